@@ -16,6 +16,13 @@ tuple hashes to r (shard.assign_shard_sports, asserted), so per-GPU work is
 fixed (weak scaling) and the stream is N x 64M tuples per step.
 Rank 0 prints one JSON line.
 
+A plain run sets up, warms up, times the steps and prints the headline line
+(metric, value, ms_per_step, kernel_ms).  --full adds everything that needs
+the CPU restatement or runs of its own: parity of the last step against the
+restatement, the CPU baselines, the roofline, the host link rates of
+--host-tuples and the N > 1 all-reduce / table checks.  --dump-outputs DIR
+writes the last timed step's results as DIR/<name>.npy.
+
 Other BASELINE configs (not the headline line; run them explicitly):
   --config cascade   config 5 whole, "prefilter -> ipcache -> policy -> LB":
                      the netdev's XDP prefilter (bpf_xdp.c check_v4: 16k dyn4
@@ -329,6 +336,42 @@ def roofline(n, kern_ms, b_in, b_out, probes_total, split, tbytes, v6, dom):
             "ceilings": f"{os.path.relpath(CEILINGS, ROOT)}: {ceil.get('source')}"}
 
 
+DUMP_BYTES = 48 << 20  # --dump-outputs: the files together stay well under 64 MB
+DUMP_SEED = 0xD0C5
+
+
+def dump_outputs(path, out, n):
+    """--dump-outputs: the arrays the last timed step returned (`out`: name ->
+    tensor or ndarray of n rows, None entries skipped) as path/<name>.npy;
+    8- and 16-bit columns as float32, 32-bit ones as float64 (exact).  When
+    all n rows would exceed DUMP_BYTES, the same seeded, sorted sample of rows
+    of every array, its row numbers in sample_index.npy."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    cols = {k: v for k, v in out.items() if v is not None}
+
+    def row_bytes(v):  # of a row as written (tensor or ndarray)
+        width = v.element_size() if hasattr(v, "element_size") else v.itemsize
+        return int(np.prod(tuple(v.shape)[1:], dtype=np.int64)) * (4 if width <= 2 else 8)
+
+    per_row = sum(row_bytes(v) for v in cols.values())
+    idx = None
+    if n * per_row > DUMP_BYTES:
+        k = DUMP_BYTES // (per_row + 8)
+        idx = np.unique(np.random.Generator(np.random.PCG64(DUMP_SEED)).integers(0, n, size=k))
+        np.save(os.path.join(path, "sample_index.npy"), idx.astype(np.float64))
+    for name, v in cols.items():
+        if hasattr(v, "element_size"):  # torch tensor, on the device or page-locked
+            if idx is not None:
+                import torch
+                v = v[torch.from_numpy(idx).to(v.device)]
+            a = v.cpu().numpy()
+        else:
+            a = v if idx is None else v[idx]
+        np.save(os.path.join(path, f"{name}.npy"),
+                a.astype(np.float32 if a.dtype.itemsize <= 2 else np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -359,7 +402,18 @@ def main():
                     help="PMC summary (tools/pmc_summary.py traffic.json) to report as roofline.traffic; "
                          "default profiles/traffic_<config>.json.  Printed only when it was measured "
                          "on the library this process loaded")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the CPU restatement over the batch: parity "
+                         "of the last step's results, the CPU baselines, the roofline (and, with "
+                         "--host-tuples, the link rates; at N > 1 the all-reduce and table checks). "
+                         "Without it the run times the steps and prints the headline line only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step returned as DIR/<name>.npy (float32 / "
+                         "float64; a fixed seeded sample of the rows, sample_index.npy, when the "
+                         "batch is larger than the 64 MB the files may take)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", 0))
     world = int(os.environ.get("WORLD_SIZE", 1))
@@ -635,9 +689,11 @@ def main():
         elapsed, kern_ms = float(tt[0]), float(tt[1])
     ms_per_step = 1e3 * elapsed / args.steps
     value = world * n * args.steps / elapsed / 1e6
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, n)
 
     allreduce_ok = None
-    if world > 1:
+    if world > 1 and args.full:
         # the shipped collective against torch's SUM of the same local deltas
         # (one untimed step): every rank must hold the sum of all ranks
         if ct and not persist:
@@ -657,7 +713,7 @@ def main():
 
     # the replicated map contents (cgpu_table_checksum) must agree across
     # ranks, and so must the counter slot layout the timed sums relied on
-    if world > 1:
+    if world > 1 and args.full:
         check_layout("after the timed steps")
         cs = torch.tensor([e.checksum() & 0x7FFFFFFFFFFFFFFF], dtype=torch.int64, device=dev)
         lo, hi = cs.clone(), cs.clone()
@@ -669,11 +725,20 @@ def main():
     # the CPU baseline is an N=1 figure (rank 0 alone); at N > 1 the
     # restatement runs once, for the parity check of rank 0's batch only
     skip_cpu = args.no_cpu_baseline or world > 1
-    if rank == 0 and args.no_parity:
-        result = {"metric": METRIC, "value": round(value, 2), "unit": "Mpps", "n_gpus": world,
+    metric = (f"Mpps classified from host-resident {'raw frames' if frames else 'batches'} (PCIe-inclusive)"
+              if args.host_tuples
+              else METRIC if not pf6 else "Mpps XDP IPv6 prefilter verdicts; % HBM roofline")
+    dtype = "u8" if pf6 else "u32"
+    if rank == 0 and (args.no_parity or not args.full):
+        # the headline line alone: no restatement, so no parity, CPU baseline
+        # or roofline (those are --full)
+        result = {"metric": metric, "value": round(value, 2), "unit": "Mpps", "n_gpus": world,
                   "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
-                  "config": {"workload": WORKLOADS[args.config], "kernel_ms": round(kern_ms, 4),
-                             "parity_vs_oracle": None, "note": "--no-parity profiling pass"}}
+                  "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": dtype,
+                  "config": {"workload": WORKLOADS[args.config], "tuples_per_gpu": n,
+                             "kernel_ms": round(kern_ms, 4), "parity_vs_oracle": None,
+                             "note": ("--no-parity profiling pass" if args.no_parity else
+                                      "timed steps only; --full adds parity, CPU baselines and roofline")}}
     elif rank == 0:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         from oracle import Oracle  # CPU restatement: checker + CPU baseline only
@@ -999,13 +1064,11 @@ def main():
                                  "connections stay established; kernel_ms is the classify alone, "
                                  "ms_per_step includes the GC calls (device GC, one host read)")})
         result = {
-            "metric": (f"Mpps classified from host-resident {'raw frames' if frames else 'batches'} (PCIe-inclusive)"
-                       if args.host_tuples
-                       else METRIC if not pf6 else "Mpps XDP IPv6 prefilter verdicts; % HBM roofline"),
+            "metric": metric,
             "value": round(value, 2), "unit": "Mpps", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "u8" if pf6 else "u32",
+            "dtype": dtype,
             "data": "synthetic (seeded PCG64 tables + tuples, SURVEY §8d)",
             "config": conf,
             "roofline": dict(roof or {"bound": None, "note": "profiles/ceilings.json absent"},
@@ -1064,7 +1127,18 @@ def bench_mapstate(args, rank, world, local):
     elapsed = time.perf_counter() - t_start
     pairs = len(eps) * len(ids)
     result = None
-    if rank == 0:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"allow": np.asarray(allow)}, len(allow))
+    if rank == 0 and not args.full:
+        result = {
+            "metric": "M (endpoint, identity) L3 policy decisions/s (computeDesiredL3PolicyMapEntries)",
+            "value": round(world * pairs * args.steps / elapsed / 1e6, 2), "unit": "M decisions/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(1e3 * elapsed / args.steps, 3),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32",
+            "config": {"workload": WORKLOADS["mapstate"], "parity_vs_oracle": None,
+                       "note": "timed steps only; --full adds parity, the CPU baseline and roofline"}}
+    elif rank == 0:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         from oracle import Oracle
         c0 = time.perf_counter()

@@ -10,7 +10,7 @@ CONFIGS=${@:-gpu cascade pf6 v6 frames ct mapstate}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 for C in $CONFIGS; do
-  timeout -k 10 400 python -u bench.py --config $C --steps 20 --warmup 3 > $OUT/bench_$C.json 2> $OUT/bench_$C.err
+  timeout -k 10 400 python -u bench.py --full --config $C --steps 20 --warmup 3 > $OUT/bench_$C.json 2> $OUT/bench_$C.err
   rc=$?; echo "bench $C rc=$rc"; cat $OUT/bench_$C.json
   [ $rc -eq 0 ] || exit $rc
 done

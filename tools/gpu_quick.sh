@@ -16,12 +16,12 @@ fi
 for C in $CONFS; do
   NAME=${C%%:*}; EXTRA=${C#*:}; [ "$EXTRA" = "$C" ] && EXTRA=""
   TAGC=$NAME$(echo "$EXTRA" | tr -d ' -')
-  timeout -k 10 400 python -u bench.py --config $NAME --steps 20 --warmup 3 $EXTRA > $OUT/bench_$TAGC.json 2> $OUT/bench_$TAGC.err
+  timeout -k 10 400 python -u bench.py --full --config $NAME --steps 20 --warmup 3 $EXTRA > $OUT/bench_$TAGC.json 2> $OUT/bench_$TAGC.err
   rc=$?; echo "bench $C rc=$rc"; cut -c1-300 $OUT/bench_$TAGC.json
   [ $rc -eq 0 ] || exit $rc
 done
 if [ -n "$TRACE" ]; then
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- python3 bench.py --config $TRACE --steps 10 --warmup 2 --no-cpu-baseline > $OUT/trace_bench.json 2> $OUT/trace_bench.err
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- python3 bench.py --full --config $TRACE --steps 10 --warmup 2 --no-cpu-baseline > $OUT/trace_bench.json 2> $OUT/trace_bench.err
   rc=$?; echo "trace rc=$rc"
   exit $rc
 fi

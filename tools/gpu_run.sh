@@ -19,7 +19,7 @@ timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $OUT/s
 rc=$?
 echo "smoke rc=$rc"; tail -2 $OUT/smoke.log
 [ $rc -le 1 ] || exit $rc
-timeout -k 10 300 python -u bench.py --steps 20 --warmup 3 > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 3 > $OUT/bench.json 2> $OUT/bench.err
 rc=$?
 echo "bench rc=$rc"; cat $OUT/bench.json
 exit $rc

@@ -16,7 +16,7 @@ fi
 for C in $CONFS; do
   NAME=${C%%:*}; EXTRA=${C#*:}; [ "$EXTRA" = "$C" ] && EXTRA=""
   TAGC=$NAME$(echo "$EXTRA" | tr -d ' -')
-  timeout -k 10 400 python -u bench.py --config $NAME --steps 20 --warmup 3 $EXTRA > $OUT/bench_$TAGC.json 2> $OUT/bench_$TAGC.err
+  timeout -k 10 400 python -u bench.py --full --config $NAME --steps 20 --warmup 3 $EXTRA > $OUT/bench_$TAGC.json 2> $OUT/bench_$TAGC.err
   rc=$?; echo "bench $C rc=$rc"; cut -c1-200 $OUT/bench_$TAGC.json
   [ $rc -eq 0 ] || exit $rc
 done

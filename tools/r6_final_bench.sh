@@ -9,7 +9,7 @@ OUT=gpurun_out/r6_final
 mkdir -p $OUT
 one() {  # name, limit, args...
   N=$1; T=$2; shift 2
-  timeout -k 10 $T python -u bench.py "$@" > $OUT/bench_$N.json 2> $OUT/bench_$N.err
+  timeout -k 10 $T python -u bench.py --full "$@" > $OUT/bench_$N.json 2> $OUT/bench_$N.err
   rc=$?; echo "bench $N rc=$rc"; cut -c1-160 $OUT/bench_$N.json
   [ $rc -eq 0 ] || exit $rc
 }

@@ -1,5 +1,6 @@
 set -e
-mkdir -p gpurun_out/r6_j
+OUT=${OUT:-bench_out/r6_j}
+mkdir -p $OUT
 for c in cascade v6 pf6 gpu; do
-  timeout -k 10 300 python -u bench.py --config $c --host-tuples --steps 5 --warmup 2 --no-cpu-baseline > gpurun_out/r6_j/host_$c.json 2> gpurun_out/r6_j/host_$c.err
+  timeout -k 10 300 python -u bench.py --full --config $c --host-tuples --steps 5 --warmup 2 --no-cpu-baseline > $OUT/host_$c.json 2> $OUT/host_$c.err
 done

@@ -17,7 +17,7 @@ if [ -n "$AB" ]; then
   [ $rc -eq 0 ] || exit $rc
 fi
 for C in $CONFS; do
-  timeout -k 10 400 python -u bench.py --config $C --steps 20 --warmup 3 > $OUT/bench_$C.json 2> $OUT/bench_$C.err
+  timeout -k 10 400 python -u bench.py --full --config $C --steps 20 --warmup 3 > $OUT/bench_$C.json 2> $OUT/bench_$C.err
   rc=$?; echo "bench $C rc=$rc"; cut -c1-200 $OUT/bench_$C.json
   [ $rc -eq 0 ] || exit $rc
 done
