@@ -34,7 +34,7 @@ class CgpuConfig(C.Structure):
         ("lb_flags", C.c_uint32),
         ("node_mac", C.c_uint8 * 6), ("reserved1", C.c_uint8 * 2),
         ("ct_max", C.c_uint32), ("schedule", C.c_uint32), ("ct6_max", C.c_uint32),
-        ("ct_lru", C.c_uint32), ("reserved", C.c_uint32 * 1),
+        ("ct_lru", C.c_uint32), ("ipcache_tunnel", C.c_uint32),
     ]
 
 
@@ -95,6 +95,8 @@ PROTOS = {
     "cgpu_ipcache_get_next_key": (i32, [vp, vp, vp]),
     "cgpu_ipcache_count": (sz, [vp]),
     "cgpu_ipcache_update_batch": (i32, [vp, vp, vp, sz, u64]),
+    "cgpu_ipcache_lookup_v4": (i32, [vp, vp, sz, vp, vp, vp, vp]),
+    "cgpu_ipcache_lookup_v6": (i32, [vp, vp, sz, vp, vp, vp, vp]),
     "cgpu_policy_update": (i32, [vp, u32, vp, vp, u64]),
     "cgpu_policy_delete": (i32, [vp, u32, vp]),
     "cgpu_policy_lookup": (i32, [vp, u32, vp, vp]),
@@ -139,6 +141,8 @@ PROTOS = {
     "cgpu_classify_v4": (i32, [vp, C.POINTER(TuplesV4), sz, vp, vp, vp, vp]),
     "cgpu_classify_v4_host": (i32, [vp, C.POINTER(TuplesV4), sz, vp, vp, vp, vp]),
     "cgpu_classify_v6": (i32, [vp, C.POINTER(TuplesV6), sz, vp, vp, vp, vp]),
+    "cgpu_classify_v4_tun": (i32, [vp, C.POINTER(TuplesV4), vp, vp, i32, sz, vp, vp, vp, vp, vp]),
+    "cgpu_classify_v6_tun": (i32, [vp, C.POINTER(TuplesV6), vp, vp, i32, sz, vp, vp, vp, vp, vp]),
     "cgpu_classify_v6_lb": (i32, [vp, C.POINTER(TuplesV6), vp, vp, sz, vp, vp, vp, vp]),
     "cgpu_classify_v4_lb": (i32, [vp, C.POINTER(TuplesV4), vp, vp, sz, vp, vp, vp, vp]),
     "cgpu_classify_v4_cascade": (i32, [vp, C.POINTER(TuplesV4), vp, vp, sz, vp, vp, vp, vp]),
@@ -166,6 +170,8 @@ PROTOS = {
     "cgpu_ct_stats": (i32, [vp, C.c_int, vp]),
     "cgpu_ct4_flush": (i32, [vp]),
     "cgpu_classify_v4_ct": (i32, [vp, C.POINTER(TuplesV4Ct), sz, u32, vp, vp, vp, vp, vp]),
+    "cgpu_classify_v4_ct_tun": (i32, [vp, C.POINTER(TuplesV4Ct), sz, u32, vp, vp, vp, vp, vp, vp]),
+    "cgpu_classify_v6_ct_tun": (i32, [vp, C.POINTER(TuplesV6Ct), sz, u32, vp, vp, vp, vp, vp, vp]),
     "cgpu_classify_v4_ctlb": (i32, [vp, C.POINTER(TuplesV4Ct), vp, sz, u32, C.POINTER(CtlbOut), vp]),
     "cgpu_ct6_update": (i32, [vp, vp, vp, u64]),
     "cgpu_ct6_delete": (i32, [vp, vp]),

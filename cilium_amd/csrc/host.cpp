@@ -142,11 +142,21 @@ struct SlotInit {
 /* ---------------- DIR-24-8 builder ---------------- */
 struct Dir248 {
 	std::vector<uint32_t> tbl24, tbl8, vals;
-	void init() { tbl24.assign(DIR_TBL24_ENTRIES, 0u); tbl8.clear(); vals.clear(); }
+	/* share: equal values >= 2^30 take one vals word (the tunnel tables of
+	 * tables.h ipc_tun; the identity tables keep one word per entry) */
+	bool share = false;
+	std::unordered_map<uint32_t, uint32_t> shared;
+	void init() { tbl24.assign(DIR_TBL24_ENTRIES, 0u); tbl8.clear(); vals.clear(); shared.clear(); }
 	uint32_t encode(uint32_t label)
 	{
 		if (label < (1u << DIR_TAG_SHIFT))
 			return DIR_TAG_DIRECT | label;
+		if (share) {
+			auto it = shared.find(label);
+			if (it != shared.end())
+				return DIR_TAG_INDIRECT | it->second;
+			shared.emplace(label, (uint32_t)vals.size());
+		}
 		vals.push_back(label);
 		return DIR_TAG_INDIRECT | (uint32_t)(vals.size() - 1);
 	}
@@ -340,6 +350,7 @@ struct Rank4 {
 	uint32_t addr; /* host order */
 	uint32_t len;
 	uint32_t label;
+	uint32_t tunnel; /* the entry's tunnel_endpoint (ipcache candidates only) */
 };
 
 /* ---------------- device arena ---------------- */
@@ -400,13 +411,13 @@ bool ipc4_candidate(const cgpu_ipcache_key &raw, uint32_t label, Rank4 *r)
 	return true;
 }
 
-void build_dir(std::vector<Rank4> cand, Dir248 &d, bool any_match)
+void build_dir(std::vector<Rank4> cand, Dir248 &d, bool any_match, bool tun = false)
 {
 	std::stable_sort(cand.begin(), cand.end(),
 			 [](const Rank4 &a, const Rank4 &b) { return a.rank < b.rank; });
 	d.init();
 	for (auto &r : cand)
-		d.apply(r.addr, r.len, any_match ? (DIR_TAG_DIRECT | 1u) : d.encode(r.label));
+		d.apply(r.addr, r.len, any_match ? (DIR_TAG_DIRECT | 1u) : d.encode(tun ? r.tunnel : r.label));
 }
 
 /* One ipcache change recompiled over the address range of its prefix: the
@@ -417,17 +428,18 @@ void build_dir(std::vector<Rank4> cand, Dir248 &d, bool any_match)
 struct Ipc4Patch {
 	uint32_t addr, len;     /* host order, IP prefix length */
 	bool has_cover;
-	uint32_t cover_label;
+	uint32_t cover_label, cover_tunnel;
 	std::vector<Rank4> subs;
 };
 
-void apply_ipc4_patch(const Ipc4Patch &pt, Dir248 &d, Lpm16cBuild &lc)
+/* tun: the same patch of the tunnel tables (tables.h ipc_tun) */
+void apply_ipc4_patch(const Ipc4Patch &pt, Dir248 &d, Lpm16cBuild &lc, bool tun = false)
 {
-	d.apply(pt.addr, pt.len, pt.has_cover ? d.encode(pt.cover_label) : 0u);
+	d.apply(pt.addr, pt.len, pt.has_cover ? d.encode(tun ? pt.cover_tunnel : pt.cover_label) : 0u);
 	std::vector<Rank4> subs = pt.subs;
 	std::stable_sort(subs.begin(), subs.end(), [](const Rank4 &a, const Rank4 &b) { return a.rank < b.rank; });
 	for (auto &r : subs)
-		d.apply(r.addr, r.len, d.encode(r.label));
+		d.apply(r.addr, r.len, d.encode(tun ? r.tunnel : r.label));
 	const uint32_t last = pt.len ? pt.addr + ((pt.len == 32 ? 1u : (1u << (32 - pt.len))) - 1u) : 0xFFFFFFFFu;
 	lc.patch(pt.addr >> 16, last >> 16, d.tbl24, d.tbl8);
 }
@@ -727,6 +739,7 @@ struct Rank6 {
 	uint32_t len;  /* IP prefix length 0..128 (static entries: 0) */
 	std::array<uint8_t, 16> addr;
 	uint32_t label;
+	uint32_t tunnel; /* the entry's tunnel_endpoint (ipcache candidates only) */
 };
 
 struct V6Build {
@@ -737,6 +750,7 @@ struct V6Build {
 	std::vector<uint32_t> bl64; /* bloom of the /64s with records (tables.h v6_lpm) */
 	bool any = false;
 	bool too_big = false; /* node lines past V6T_LINE_MASK */
+	std::unordered_map<uint32_t, uint32_t> shared; /* tunnel trie: value -> vals word */
 };
 
 uint32_t v6_encode(std::vector<uint32_t> &vals, uint32_t label)
@@ -920,7 +934,7 @@ void hop_place(std::vector<std::array<uint32_t, W>> &tab, uint32_t &mask,
 	       const std::vector<std::array<uint32_t, W>> &recs, uint32_t (*home_of)(const std::array<uint32_t, W> &));
 
 /* Longest-prefix trie over (rank, len, address) candidates; see tables.h v6_lpm. */
-void build_v6(std::vector<Rank6> cand, V6Build &b)
+void build_v6(std::vector<Rank6> cand, V6Build &b, bool tun = false)
 {
 	b.any = !cand.empty();
 	if (!b.any)
@@ -941,8 +955,22 @@ void build_v6(std::vector<Rank6> cand, V6Build &b)
 	for (uint32_t i = 0; i < ord.size(); i++)
 		ord[i] = i;
 	std::stable_sort(ord.begin(), ord.end(), [&](uint32_t x, uint32_t y) { return cand[x].rank < cand[y].rank; });
-	for (uint32_t i : ord) /* vals in rank order (as the DIR builds) */
-		ps[i].enc = v6_encode(b.vals, cand[i].label);
+	for (uint32_t i : ord) { /* vals in rank order (as the DIR builds) */
+		if (!tun) {
+			ps[i].enc = v6_encode(b.vals, cand[i].label);
+			continue;
+		}
+		/* the tunnel trie (tables.h ipc_tun): equal values share a word */
+		const uint32_t t = cand[i].tunnel;
+		auto it = t < (1u << DIR_TAG_SHIFT) ? b.shared.end() : b.shared.find(t);
+		if (it != b.shared.end()) {
+			ps[i].enc = DIR_TAG_INDIRECT | it->second;
+			continue;
+		}
+		ps[i].enc = v6_encode(b.vals, t);
+		if (t >= (1u << DIR_TAG_SHIFT))
+			b.shared.emplace(t, (uint32_t)b.vals.size() - 1u);
+	}
 	std::vector<T6> srt(ps);
 	std::stable_sort(srt.begin(), srt.end(), [](const T6 &x, const T6 &y) {
 		return x.hi != y.hi ? x.hi < y.hi : (x.lo != y.lo ? x.lo < y.lo : x.rank < y.rank);
@@ -1862,6 +1890,14 @@ struct BuildState {
 	Dir248 dir;       /* ipcache v4 DIR-24-8 (host only) */
 	Lpm16cBuild lc;   /* its compressed form (uploaded) */
 	V6Build v6;
+	/* cgpu_config.ipcache_tunnel: the same three over the entries' tunnel
+	 * words (tables.h ipc_tun), built and patched with the identity images;
+	 * tun: their device form in the newest compiled group buffer */
+	Dir248 dirT;
+	Lpm16cBuild lcT;
+	V6Build v6T;
+	ipc_tun tun{};
+	uint64_t ipc_builds = 0, ipc_patched = 0; /* IPv4 full builds / patch commits (cgpu_diag_ipc_commits) */
 	bool pol_ok = false;
 	PolBuild pol;
 	PgBuild pg;
@@ -2000,6 +2036,7 @@ struct Epoch {
 	cgpu_ctx *c = nullptr;
 	uint64_t id = 0;
 	cgpu_snapshot snap{};
+	ipc_tun tun{}; /* into bufs[G_IPC]; t4.d16 == NULL without cgpu_config.ipcache_tunnel */
 	DevBufP bufs[G_N];
 	hipEvent_t ready = nullptr;
 	std::mutex mu;
@@ -3265,12 +3302,15 @@ static void ipc_family(const cgpu_ctx *c, const uint8_t *stat, std::vector<R> &o
 static void capture_ipc(cgpu_ctx *c, CommitIn &in, const BuildState &b)
 {
 	auto c4 = [](const IpcEntry &e, const LpmKey<20> &, Rank4 *r) {
+		r->tunnel = e.val.tunnel_endpoint;
 		return ipc4_candidate(e.raw, e.val.sec_label, r);
 	};
 	auto c6 = [](const IpcEntry &e, const LpmKey<20> &k, Rank6 *r) {
-		return ipc6_candidate(e.raw, k.data.data(), e.val.sec_label, r);
+		const bool ok = ipc6_candidate(e.raw, k.data.data(), e.val.sec_label, r);
+		r->tunnel = e.val.tunnel_endpoint;
+		return ok;
 	};
-	in.ipc4_full = c->ipc_full || !b.ipc4_ok || b.lc.bloated();
+	in.ipc4_full = c->ipc_full || !b.ipc4_ok || b.lc.bloated() || (c->cfg.ipcache_tunnel && b.lcT.bloated());
 	in.ipc6_build = c->ipc_full || !b.ipc4_ok;
 	std::set<LpmKey<20>> seen;
 	for (const auto &k : c->ipc_changes) {
@@ -3298,12 +3338,13 @@ static void capture_ipc(cgpu_ctx *c, CommitIn &in, const BuildState &b)
 		memcpy(&a, d + 4, 4);
 		pt.addr = bswap32(a);
 		pt.has_cover = false;
-		pt.cover_label = 0;
+		pt.cover_label = pt.cover_tunnel = 0;
 		for (int64_t l = (int64_t)pt.len - 1; l >= 0 && !pt.has_cover; l--) {
 			auto it = c->ipc.find(lpm_canon<20>(32 + (uint32_t)l, d));
 			if (it != c->ipc.end()) {
 				pt.has_cover = true;
 				pt.cover_label = it->second.val.sec_label;
+				pt.cover_tunnel = it->second.val.tunnel_endpoint;
 			}
 		}
 		for (int64_t p = 31; p >= 0 && !pt.has_cover; p--) {
@@ -3311,6 +3352,7 @@ static void capture_ipc(cgpu_ctx *c, CommitIn &in, const BuildState &b)
 			if (it != c->ipc.end() && prefix_eq(it->first.data.data(), kStaticV4, (uint32_t)p)) {
 				pt.has_cover = true;
 				pt.cover_label = it->second.val.sec_label;
+				pt.cover_tunnel = it->second.val.tunnel_endpoint;
 			}
 		}
 		/* every entry inside the range (this key included, if present) */
@@ -3329,8 +3371,10 @@ static void capture_ipc(cgpu_ctx *c, CommitIn &in, const BuildState &b)
 				break;
 			Rank4 r;
 			if (it->first.plen >= k.plen && it->first.plen <= 64 &&
-			    ipc4_candidate(it->second.raw, it->second.val.sec_label, &r))
+			    ipc4_candidate(it->second.raw, it->second.val.sec_label, &r)) {
+				r.tunnel = it->second.val.tunnel_endpoint;
 				pt.subs.push_back(r);
+			}
 		}
 		in.ipc4_patches.push_back(std::move(pt));
 	}
@@ -3518,29 +3562,52 @@ template <typename T> static const T *at(const DevBufP &b, size_t off)
 	return reinterpret_cast<const T *>(static_cast<const char *>(b->p) + off);
 }
 
+/* the host images of group IPC brought up to the captured mirror: a full
+ * build, or the captured patches applied in place (also cgpu_diag_ipc_tunnel) */
+static void compile_ipc(BuildState &b, CommitIn &in)
+{
+	const bool tun = in.cfg.ipcache_tunnel != 0;
+	if (in.ipc4_full) {
+		if (tun) {
+			b.dirT.share = true;
+			build_dir(in.ipc4_cand, b.dirT, false, true);
+			b.lcT.build(b.dirT.tbl24, b.dirT.tbl8);
+		}
+		build_dir(std::move(in.ipc4_cand), b.dir, false);
+		b.lc.build(b.dir.tbl24, b.dir.tbl8);
+		b.ipc4_ok = true;
+		b.ipc_builds++;
+	} else {
+		for (auto &pt : in.ipc4_patches) {
+			apply_ipc4_patch(pt, b.dir, b.lc);
+			if (tun)
+				apply_ipc4_patch(pt, b.dirT, b.lcT, true);
+		}
+		b.ipc_patched++;
+	}
+	if (in.ipc6_build) {
+		if (tun) {
+			b.v6T = V6Build();
+			build_v6(in.ipc6_cand, b.v6T, true);
+		}
+		b.v6 = V6Build();
+		build_v6(std::move(in.ipc6_cand), b.v6);
+	}
+}
+
 /* group IPC: compressed ipcache v4 (+ DIR-24-8 leaves' vals) and v6 LPM */
 static int commit_ipc(cgpu_ctx *c, CommitIn &in, cgpu_snapshot &s, DevBufP &buf)
 {
 	BuildState &b = c->b;
-	if (in.ipc4_full) {
-		build_dir(std::move(in.ipc4_cand), b.dir, false);
-		b.lc.build(b.dir.tbl24, b.dir.tbl8);
-		b.ipc4_ok = true;
-	} else {
-		for (auto &pt : in.ipc4_patches)
-			apply_ipc4_patch(pt, b.dir, b.lc);
-	}
-	if (in.ipc6_build) {
-		b.v6 = V6Build();
-		build_v6(std::move(in.ipc6_cand), b.v6);
-	}
+	const bool tun = in.cfg.ipcache_tunnel != 0;
+	compile_ipc(b, in);
 	Arena ar;
 	const size_t o_x = ar.add(b.lc.x16.data(), b.lc.x16.size() * 4);
 	const size_t o_d = ar.add(b.lc.d16.data(), b.lc.d16.size() * 4);
 	const size_t o_n = ar.add(b.lc.nodes.data(), b.lc.nodes.size() * 4);
 	const size_t o_c = ar.add(b.lc.dict.data(), b.lc.dict.size() * 4);
 	const size_t o_v = ar.add(b.dir.vals.data(), b.dir.vals.size() * 4);
-	if (b.v6.too_big)
+	if (b.v6.too_big || (tun && b.v6T.too_big))
 		return fail(-E2BIG, "ipcache v6 trie exceeds 2^29 node lines");
 	size_t o6[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
 	if (b.v6.any) {
@@ -3553,6 +3620,28 @@ static int commit_ipc(cgpu_ctx *c, CommitIn &in, cgpu_snapshot &s, DevBufP &buf)
 		o6[6] = ar.add(b.v6.rbits.data(), b.v6.rbits.size() * 4);
 		o6[7] = ar.add(b.v6.b24_16.data(), b.v6.b24_16.size() * 2);
 		o6[8] = ar.add(b.v6.bl64.data(), b.v6.bl64.size() * 4);
+	}
+	/* the tunnel tables (tables.h ipc_tun) behind the identity tables, whose
+	 * offsets they leave as they are; in the same group buffer, so the upload
+	 * sum and cgpu_table_verify cover them */
+	size_t oT[5] = {0, 0, 0, 0, 0}, oT6[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+	if (tun) {
+		oT[0] = ar.add(b.lcT.x16.data(), b.lcT.x16.size() * 4);
+		oT[1] = ar.add(b.lcT.d16.data(), b.lcT.d16.size() * 4);
+		oT[2] = ar.add(b.lcT.nodes.data(), b.lcT.nodes.size() * 4);
+		oT[3] = ar.add(b.lcT.dict.data(), b.lcT.dict.size() * 4);
+		oT[4] = ar.add(b.dirT.vals.data(), b.dirT.vals.size() * 4);
+		if (b.v6T.any) {
+			oT6[0] = ar.add(b.v6T.root.data(), b.v6T.root.size() * 4);
+			oT6[1] = ar.add(b.v6T.b24.data(), b.v6T.b24.size() * 4);
+			oT6[2] = ar.add(b.v6T.b32.data(), b.v6T.b32.size() * 4);
+			oT6[3] = ar.add(b.v6T.pool.data(), b.v6T.pool.size() * 4);
+			oT6[4] = ar.add(b.v6T.vals.data(), b.v6T.vals.size() * 4);
+			oT6[5] = ar.add(b.v6T.h64.data(), b.v6T.h64.size() * 32);
+			oT6[6] = ar.add(b.v6T.rbits.data(), b.v6T.rbits.size() * 4);
+			oT6[7] = ar.add(b.v6T.b24_16.data(), b.v6T.b24_16.size() * 2);
+			oT6[8] = ar.add(b.v6T.bl64.data(), b.v6T.bl64.size() * 4);
+		}
 	}
 	if (int r = upload(c, ar, buf, G_IPC))
 		return r;
@@ -3574,6 +3663,24 @@ static int commit_ipc(cgpu_ctx *c, CommitIn &in, cgpu_snapshot &s, DevBufP &buf)
 				b.v6.b24_16.empty() ? nullptr : at<uint16_t>(buf, o6[7]),
 				(uint32_t)(b.v6.b24.size() / 256), at<uint32_t>(buf, o6[8]),
 				(uint32_t)b.v6.bl64.size() - 1u};
+	b.tun = ipc_tun{};
+	if (tun) {
+		/* the tunnel lookups read every level from device memory */
+		buf->gather += (b.lcT.x16.size() + b.lcT.nodes.size() + b.lcT.dict.size() + b.dirT.vals.size()) * 4;
+		b.tun.t4 = lpm16c{at<uint32_t>(buf, oT[1]), at<uint32_t>(buf, oT[2]), at<uint32_t>(buf, oT[4]),
+				  at<uint32_t>(buf, oT[0]), at<uint32_t>(buf, oT[3]), (uint32_t)b.lcT.nodes.size(),
+				  (uint32_t)b.lcT.dict.size()};
+		if (b.v6T.any) {
+			buf->gather += (b.v6T.root.size() + b.v6T.b24.size() + b.v6T.b32.size() + b.v6T.pool.size() +
+					b.v6T.vals.size()) * 4 + b.v6T.h64.size() * 32;
+			b.tun.t6 = v6_lpm{at<uint32_t>(buf, oT6[0]), at<uint32_t>(buf, oT6[1]), at<uint2>(buf, oT6[2]),
+					  at<uint32_t>(buf, oT6[3]), at<uint32_t>(buf, oT6[4]), at<uint4>(buf, oT6[5]),
+					  b.v6T.m64, at<uint32_t>(buf, oT6[6]),
+					  b.v6T.b24_16.empty() ? nullptr : at<uint16_t>(buf, oT6[7]),
+					  (uint32_t)(b.v6T.b24.size() / 256), at<uint32_t>(buf, oT6[8]),
+					  (uint32_t)b.v6T.bl64.size() - 1u};
+		}
+	}
 	b.sum[G_IPC] = in.sum_ipc;
 	return 0;
 }
@@ -3913,6 +4020,7 @@ static int commit_locked(cgpu_ctx *c, uint64_t *epoch_out)
 	e->id = in.id;
 	if (prev) {
 		e->snap = prev->snap;
+		e->tun = prev->tun;
 		for (int k = 0; k < G_N; k++)
 			e->bufs[k] = prev->bufs[k];
 	}
@@ -3930,6 +4038,8 @@ static int commit_locked(cgpu_ctx *c, uint64_t *epoch_out)
 			if (rc && k == G_POL)
 				c->b.pol_ok = false;
 		}
+	if (!rc && (in.dirty & (1u << G_IPC)))
+		e->tun = c->b.tun;
 	if (!rc)
 		rc = commit_inits(c, in);
 	hipError_t he = hipSuccess;
@@ -4240,6 +4350,126 @@ CGPU_EXPORT int cgpu__test_corrupt(cgpu_ctx *c, int group, size_t off, uint8_t m
 	return 0;
 }
 
+/* The device lookup (kernels.hip lpmc_lookup) restated over an Lpm16cBuild
+ * on the host (h: the address in host order): cgpu_diag_ipc_tunnel */
+static uint32_t lpmc_host_lookup(const Lpm16cBuild &t, uint32_t h)
+{
+	const uint32_t *q = &t.x16[(size_t)(h >> 16) * 4];
+	if (!(q[3] & LPMC_OVERFLOW)) {
+		const uint32_t x = h & 0xFFFFu;
+		const uint32_t cnt = (x >= (q[0] & 0xFFFFu)) + (x >= (q[0] >> 16)) + (x >= (q[1] & 0xFFFFu)) +
+				     (x >= (q[1] >> 16));
+		const uint64_t v = ((uint64_t)q[3] << 32) | q[2];
+		return t.dict[(uint32_t)(v >> (12u * cnt)) & 0xFFFu];
+	}
+	const uint32_t ARR = (DIR_TAG_GROUP >> LPMC_KIND_SHIFT) | 3u;
+	uint32_t e = q[0];
+	bool lvl8 = false;
+	if ((e >> LPMC_KIND_SHIFT) == ARR) {
+		e = t.nodes[(size_t)(e & LPMC_OFF_MASK) * 4u + ((h >> 8) & 255u)];
+		lvl8 = true;
+		if ((e >> LPMC_KIND_SHIFT) == ARR)
+			e = t.nodes[(size_t)(e & LPMC_OFF_MASK) * 4u + (h & 255u)];
+	}
+	if ((e & DIR_TAG_MASK) == DIR_TAG_GROUP) {
+		const uint32_t kind = (e >> LPMC_KIND_SHIFT) & 3u;
+		const uint32_t nb = kind == 0 ? 1u : (kind == 1 ? 2u : 5u);
+		const uint32_t *w = &t.nodes[(size_t)(e & LPMC_OFF_MASK) * 4u];
+		const uint32_t x = lvl8 ? (h & 255u) : (h & 0xFFFFu);
+		uint32_t cnt = 0;
+		for (uint32_t i = 0; i < nb; i++)
+			cnt += (x >= (w[i] & 0xFFFFu)) + (x >= (w[i] >> 16));
+		e = w[nb + cnt];
+	}
+	return e;
+}
+
+static uint32_t leaf_value(const std::vector<uint32_t> &vals, uint32_t e)
+{
+	return (e & DIR_TAG_MASK) == DIR_TAG_INDIRECT ? vals[e & DIR_PAYLOAD_MASK] : e & DIR_PAYLOAD_MASK;
+}
+
+/* Test hook (not part of the drop-in boundary, no header): the ipcache's
+ * identity and tunnel tables compiled as cgpu_commit compiles them with
+ * cgpu_config.ipcache_tunnel set, on a host-only context, and walked on the
+ * host as the kernels walk them.  The first n_first entries are one commit,
+ * the other n - n_first a second one (which patches in place where a commit
+ * would); del[i] != 0 (del may be NULL) deletes key i instead of updating it.
+ * addrs: m network-order u32 (v6 = 0) or m x 16 bytes.  out[3 j ..]:
+ * {found, sec_label, tunnel_endpoint} of the longest match, the ipcache_lookup4
+ * / 6 answer (eps.h:56-80).  commits (may be NULL): {IPv4 full builds, commits
+ * that patched}. */
+CGPU_EXPORT int cgpu_diag_ipc_tunnel(const cgpu_ipcache_key *keys, const cgpu_remote_endpoint_info *vals,
+				     const uint8_t *del, size_t n, size_t n_first, const void *addrs, size_t m,
+				     int v6, uint32_t *out, uint64_t *commits)
+{
+	if ((n && (!keys || !vals)) || (m && (!addrs || !out)) || n_first > n)
+		return fail(-EINVAL, "null argument");
+	cgpu_config cfg;
+	cgpu_config_default(&cfg);
+	cfg.ipcache_tunnel = 1;
+	cfg.ipcache_max = (uint32_t)std::max<size_t>(n, 1);
+	cgpu_ctx *c = nullptr;
+	if (int r = cgpu_ctx_create(&cfg, -1, &c))
+		return r;
+	int rc = 0;
+	for (int phase = 0; phase < 2 && !rc; phase++) {
+		const size_t lo = phase ? n_first : 0, hi = phase ? n : n_first;
+		if (phase && lo == hi)
+			break;
+		for (size_t i = lo; i < hi && !rc; i++) {
+			rc = del && del[i] ? cgpu_ipcache_delete(c, &keys[i]) : cgpu_ipcache_update(c, &keys[i], &vals[i], CGPU_ANY);
+		}
+		if (rc)
+			break;
+		CommitIn in;
+		in.cfg = c->cfg;
+		{
+			std::lock_guard<std::mutex> g(c->mu);
+			capture_ipc(c, in, c->b);
+		}
+		compile_ipc(c->b, in);
+	}
+	const BuildState &b = c->b;
+	if (!rc && (b.v6.too_big || b.v6T.too_big))
+		rc = -E2BIG;
+	for (size_t j = 0; j < m && !rc; j++) {
+		uint32_t e, t;
+		if (v6) {
+			const uint8_t *a = static_cast<const uint8_t *>(addrs) + 16 * j;
+			e = b.v6.any ? v6t_host_lookup(b.v6, a) : 0u;
+			t = b.v6T.any ? v6t_host_lookup(b.v6T, a) : 0u;
+			out[3 * j + 1] = leaf_value(b.v6.vals, e);
+			out[3 * j + 2] = e ? leaf_value(b.v6T.vals, t) : 0u;
+		} else {
+			const uint32_t h = bswap32(static_cast<const uint32_t *>(addrs)[j]);
+			e = lpmc_host_lookup(b.lc, h);
+			t = lpmc_host_lookup(b.lcT, h);
+			out[3 * j + 1] = leaf_value(b.dir.vals, e);
+			out[3 * j + 2] = e ? leaf_value(b.dirT.vals, t) : 0u;
+		}
+		out[3 * j] = e != 0u;
+	}
+	if (commits) {
+		commits[0] = b.ipc_builds;
+		commits[1] = b.ipc_patched;
+	}
+	cgpu_ctx_destroy(c);
+	return rc;
+}
+
+/* Test hook (no header): {IPv4 ipcache full builds, ipcache commits that
+ * patched the tables in place} of the context so far */
+CGPU_EXPORT int cgpu_diag_ipc_commits(cgpu_ctx *c, uint64_t *out)
+{
+	if (!c || !out)
+		return fail(-EINVAL, "null argument");
+	std::lock_guard<std::mutex> cg(c->commit_mu);
+	out[0] = c->b.ipc_builds;
+	out[1] = c->b.ipc_patched;
+	return 0;
+}
+
 CGPU_EXPORT int cgpu_counter_layout_checksum(cgpu_ctx *c, uint64_t *sum)
 {
 	if (!c || !sum)
@@ -4267,6 +4497,7 @@ struct Pinned {
 	hipStream_t st = nullptr;
 	uint64_t *delta = nullptr, *pk = nullptr;
 	const cgpu_snapshot &snap() const { return ep->snap; }
+	const ipc_tun &tun() const { return ep->tun; }
 	~Pinned()
 	{
 		if (!ep)
@@ -4356,8 +4587,26 @@ CGPU_EXPORT int cgpu_stream_release(cgpu_ctx *c, void *stream)
 	return 0;
 }
 
-CGPU_EXPORT int cgpu_classify_v4(cgpu_ctx *c, const cgpu_tuples_v4 *t, size_t n, int32_t *verdict,
-				 uint32_t *identity, uint8_t *stage, void *stream)
+/* a tunnel output needs the tunnel tables (cgpu_config.ipcache_tunnel) */
+static int check_tunnel(const cgpu_ctx *c, const void *tunnel)
+{
+	if (!c)
+		return fail(-EINVAL, "null context");
+	if (c->device < 0)
+		return fail(-ENODEV, "context has no device (host-only); no CPU classification path");
+	if (tunnel && !c->cfg.ipcache_tunnel)
+		return fail(-EINVAL, "tunnel output requested but cgpu_config.ipcache_tunnel is 0 "
+				     "(the device holds no tunnel endpoints)");
+	if ((uintptr_t)tunnel & 3u)
+		return fail(-EINVAL, "tunnel column not 4-byte aligned");
+	return 0;
+}
+
+/* the stateless IPv4 paths (cgpu.h CGPU_PATH_*); tunnel: NULL, or the [n]
+ * tunnel output of cgpu_classify_v4_tun */
+static int classify_v4_path(cgpu_ctx *c, const cgpu_tuples_v4 *t, const uint16_t *sport, const uint32_t *hash,
+			    int path, size_t n, int32_t *verdict, uint32_t *identity, uint8_t *stage,
+			    uint32_t *tunnel, void *stream)
 {
 	Pinned P;
 	if (int r = pin(c, stream, P, true))
@@ -4367,13 +4616,73 @@ CGPU_EXPORT int cgpu_classify_v4(cgpu_ctx *c, const cgpu_tuples_v4 *t, size_t n,
 	if (!t || (n && (!t->saddr || !t->daddr || !t->dport || !t->proto || !t->flags || !t->len ||
 			 !t->ep || !verdict || !identity)))
 		return fail(-EINVAL, "null tuple column or output");
+	if (path != CGPU_PATH_PLAIN && n && !hash && !sport)
+		return fail(-EINVAL, "either a hash or an sport column is needed");
 	if (!n)
 		return 0;
 	classify_v4_args a{t->saddr, t->daddr, t->dport, t->proto, t->flags, t->len, t->ep,
 			   verdict, identity, stage, delta, (uint64_t)n, pk, 0, nullptr, nullptr};
+	if (path != CGPU_PATH_PLAIN) {
+		a.lb = 1;
+		a.xdp = path == CGPU_PATH_CASCADE;
+		a.sport = sport;
+		a.hash = hash;
+	}
+	a.tunnel = tunnel;
+	a.tun = &P.tun();
 	HIP_OR_EIO(hipSetDevice(c->device));
 	HIP_OR_EIO(launch_classify_v4(s, a, (hipStream_t)stream));
 	return 0;
+}
+
+CGPU_EXPORT int cgpu_classify_v4(cgpu_ctx *c, const cgpu_tuples_v4 *t, size_t n, int32_t *verdict,
+				 uint32_t *identity, uint8_t *stage, void *stream)
+{
+	return classify_v4_path(c, t, nullptr, nullptr, CGPU_PATH_PLAIN, n, verdict, identity, stage, nullptr, stream);
+}
+
+CGPU_EXPORT int cgpu_classify_v4_tun(cgpu_ctx *c, const cgpu_tuples_v4 *t, const uint16_t *sport,
+				     const uint32_t *hash, int path, size_t n, int32_t *verdict,
+				     uint32_t *identity, uint8_t *stage, uint32_t *tunnel, void *stream)
+{
+	if (int r = check_tunnel(c, tunnel))
+		return r;
+	if (path != CGPU_PATH_PLAIN && path != CGPU_PATH_LB && path != CGPU_PATH_CASCADE)
+		return fail(-EINVAL, "bad path %d", path);
+	return classify_v4_path(c, t, sport, hash, path, n, verdict, identity, stage, tunnel, stream);
+}
+
+static int ipcache_lookup_batch(cgpu_ctx *c, const void *addr, size_t n, int v6, uint8_t *found,
+				uint32_t *sec_label, uint32_t *tunnel, void *stream)
+{
+	if (int r = check_tunnel(c, tunnel))
+		return r;
+	Pinned P;
+	if (int r = pin(c, stream, P))
+		return r;
+	if (n && !addr)
+		return fail(-EINVAL, "null address column");
+	if (!v6 && ((uintptr_t)addr & 3u))
+		return fail(-EINVAL, "IPv4 address column not 4-byte aligned");
+	if (((uintptr_t)sec_label | (uintptr_t)tunnel) & 3u)
+		return fail(-EINVAL, "output column not 4-byte aligned");
+	if (!n)
+		return 0;
+	const ipc_lookup_args a{addr, (uint64_t)n, found, sec_label, tunnel, v6};
+	HIP_OR_EIO(launch_ipcache_lookup(P.snap(), P.tun(), a, (hipStream_t)stream));
+	return 0;
+}
+
+CGPU_EXPORT int cgpu_ipcache_lookup_v4(cgpu_ctx *c, const uint32_t *addr, size_t n, uint8_t *found,
+				       uint32_t *sec_label, uint32_t *tunnel, void *stream)
+{
+	return ipcache_lookup_batch(c, addr, n, 0, found, sec_label, tunnel, stream);
+}
+
+CGPU_EXPORT int cgpu_ipcache_lookup_v6(cgpu_ctx *c, const uint8_t *addr16, size_t n, uint8_t *found,
+				       uint32_t *sec_label, uint32_t *tunnel, void *stream)
+{
+	return ipcache_lookup_batch(c, addr16, n, 1, found, sec_label, tunnel, stream);
 }
 
 /* ---- host-resident batches (host or device pointers) ----
@@ -4751,53 +5060,14 @@ CGPU_EXPORT int cgpu_classify_v4_lb(cgpu_ctx *c, const cgpu_tuples_v4 *t, const 
 				    const uint32_t *hash, size_t n, int32_t *verdict, uint32_t *identity,
 				    uint8_t *stage, void *stream)
 {
-	Pinned P;
-	if (int r = pin(c, stream, P, true))
-		return r;
-	const cgpu_snapshot &s = P.snap();
-	uint64_t *delta = P.delta, *pk = P.pk;
-	if (!t || (n && (!t->saddr || !t->daddr || !t->dport || !t->proto || !t->flags || !t->len ||
-			 !t->ep || !verdict || !identity)))
-		return fail(-EINVAL, "null tuple column or output");
-	if (n && !hash && !sport)
-		return fail(-EINVAL, "either a hash or an sport column is needed");
-	if (!n)
-		return 0;
-	classify_v4_args a{t->saddr, t->daddr, t->dport, t->proto, t->flags, t->len, t->ep,
-			   verdict, identity, stage, delta, (uint64_t)n, pk};
-	a.lb = 1;
-	a.sport = sport;
-	a.hash = hash;
-	HIP_OR_EIO(hipSetDevice(c->device));
-	HIP_OR_EIO(launch_classify_v4(s, a, (hipStream_t)stream));
-	return 0;
+	return classify_v4_path(c, t, sport, hash, CGPU_PATH_LB, n, verdict, identity, stage, nullptr, stream);
 }
 
 CGPU_EXPORT int cgpu_classify_v4_cascade(cgpu_ctx *c, const cgpu_tuples_v4 *t, const uint16_t *sport,
 					 const uint32_t *hash, size_t n, int32_t *verdict, uint32_t *identity,
 					 uint8_t *stage, void *stream)
 {
-	Pinned P;
-	if (int r = pin(c, stream, P, true))
-		return r;
-	const cgpu_snapshot &s = P.snap();
-	uint64_t *delta = P.delta, *pk = P.pk;
-	if (!t || (n && (!t->saddr || !t->daddr || !t->dport || !t->proto || !t->flags || !t->len ||
-			 !t->ep || !verdict || !identity)))
-		return fail(-EINVAL, "null tuple column or output");
-	if (n && !hash && !sport)
-		return fail(-EINVAL, "either a hash or an sport column is needed");
-	if (!n)
-		return 0;
-	classify_v4_args a{t->saddr, t->daddr, t->dport, t->proto, t->flags, t->len, t->ep,
-			   verdict, identity, stage, delta, (uint64_t)n, pk};
-	a.lb = 1;
-	a.xdp = 1;
-	a.sport = sport;
-	a.hash = hash;
-	HIP_OR_EIO(hipSetDevice(c->device));
-	HIP_OR_EIO(launch_classify_v4(s, a, (hipStream_t)stream));
-	return 0;
+	return classify_v4_path(c, t, sport, hash, CGPU_PATH_CASCADE, n, verdict, identity, stage, nullptr, stream);
 }
 
 CGPU_EXPORT int cgpu_lb4_select(cgpu_ctx *c, int mode, const cgpu_lb4_tuples *t, size_t n,
@@ -4822,8 +5092,10 @@ CGPU_EXPORT int cgpu_lb4_select(cgpu_ctx *c, int mode, const cgpu_lb4_tuples *t,
 	return 0;
 }
 
-CGPU_EXPORT int cgpu_classify_v6(cgpu_ctx *c, const cgpu_tuples_v6 *t, size_t n, int32_t *verdict,
-				 uint32_t *identity, uint8_t *stage, void *stream)
+/* the stateless IPv6 paths (CGPU_PATH_PLAIN / _LB); tunnel as classify_v4_path */
+static int classify_v6_path(cgpu_ctx *c, const cgpu_tuples_v6 *t, const uint16_t *sport, const uint32_t *hash,
+			    int path, size_t n, int32_t *verdict, uint32_t *identity, uint8_t *stage,
+			    uint32_t *tunnel, void *stream)
 {
 	Pinned P;
 	if (int r = pin(c, stream, P, true))
@@ -4835,11 +5107,22 @@ CGPU_EXPORT int cgpu_classify_v6(cgpu_ctx *c, const cgpu_tuples_v6 *t, size_t n,
 		return fail(-EINVAL, "null tuple column or output");
 	if (((uintptr_t)t->saddr | (uintptr_t)t->daddr) & 15)
 		return fail(-EINVAL, "v6 address columns must be 16-byte aligned");
+	if (path == CGPU_PATH_LB && n && !hash && !sport)
+		return fail(-EINVAL, "either a hash or an sport column is needed");
 	if (!n)
 		return 0;
 	classify_v6_args a{t->saddr, t->daddr, t->dport, t->proto, t->flags, t->len, t->ep,
 			   verdict, identity, stage, delta, (uint64_t)n, pk};
+	a.tunnel = tunnel;
+	a.tun = &P.tun();
 	HIP_OR_EIO(hipSetDevice(c->device));
+	if (path == CGPU_PATH_LB) {
+		a.lb = 1;
+		a.sport = sport;
+		a.hash = hash;
+		HIP_OR_EIO(launch_classify_v6(s, a, (hipStream_t)stream));
+		return 0;
+	}
 	/* the x4 schedule's ipcache pre-pass: n entries of stream-ordered pool
 	 * scratch */
 	void *scr = nullptr;
@@ -4856,32 +5139,28 @@ CGPU_EXPORT int cgpu_classify_v6(cgpu_ctx *c, const cgpu_tuples_v6 *t, size_t n,
 	return 0;
 }
 
+CGPU_EXPORT int cgpu_classify_v6(cgpu_ctx *c, const cgpu_tuples_v6 *t, size_t n, int32_t *verdict,
+				 uint32_t *identity, uint8_t *stage, void *stream)
+{
+	return classify_v6_path(c, t, nullptr, nullptr, CGPU_PATH_PLAIN, n, verdict, identity, stage, nullptr, stream);
+}
+
+CGPU_EXPORT int cgpu_classify_v6_tun(cgpu_ctx *c, const cgpu_tuples_v6 *t, const uint16_t *sport,
+				     const uint32_t *hash, int path, size_t n, int32_t *verdict,
+				     uint32_t *identity, uint8_t *stage, uint32_t *tunnel, void *stream)
+{
+	if (int r = check_tunnel(c, tunnel))
+		return r;
+	if (path != CGPU_PATH_PLAIN && path != CGPU_PATH_LB)
+		return fail(-EINVAL, "bad path %d (IPv6: CGPU_PATH_PLAIN or CGPU_PATH_LB)", path);
+	return classify_v6_path(c, t, sport, hash, path, n, verdict, identity, stage, tunnel, stream);
+}
+
 CGPU_EXPORT int cgpu_classify_v6_lb(cgpu_ctx *c, const cgpu_tuples_v6 *t, const uint16_t *sport,
 				    const uint32_t *hash, size_t n, int32_t *verdict, uint32_t *identity,
 				    uint8_t *stage, void *stream)
 {
-	Pinned P;
-	if (int r = pin(c, stream, P, true))
-		return r;
-	const cgpu_snapshot &s = P.snap();
-	uint64_t *delta = P.delta, *pk = P.pk;
-	if (!t || (n && (!t->saddr || !t->daddr || !t->dport || !t->proto || !t->flags || !t->len ||
-			 !t->ep || !verdict || !identity)))
-		return fail(-EINVAL, "null tuple column or output");
-	if (((uintptr_t)t->saddr | (uintptr_t)t->daddr) & 15)
-		return fail(-EINVAL, "v6 address columns must be 16-byte aligned");
-	if (n && !hash && !sport)
-		return fail(-EINVAL, "either a hash or an sport column is needed");
-	if (!n)
-		return 0;
-	classify_v6_args a{t->saddr, t->daddr, t->dport, t->proto, t->flags, t->len, t->ep,
-			   verdict, identity, stage, delta, (uint64_t)n, pk};
-	a.lb = 1;
-	a.sport = sport;
-	a.hash = hash;
-	HIP_OR_EIO(hipSetDevice(c->device));
-	HIP_OR_EIO(launch_classify_v6(s, a, (hipStream_t)stream));
-	return 0;
+	return classify_v6_path(c, t, sport, hash, CGPU_PATH_LB, n, verdict, identity, stage, nullptr, stream);
 }
 
 
@@ -6069,9 +6348,9 @@ static int ct_classify(cgpu_ctx *c, const cgpu_snapshot &s, uint64_t *delta, CtM
 	return 0;
 }
 
-CGPU_EXPORT int cgpu_classify_v4_ct(cgpu_ctx *c, const cgpu_tuples_v4_ct *t, size_t n, uint32_t now,
-				    int32_t *verdict, uint8_t *ct_ret, uint32_t *identity,
-				    uint8_t *stage, void *stream)
+/* cgpu_classify_v4_ct; tunnel: NULL, or cgpu_classify_v4_ct_tun's output */
+static int classify_v4_ct(cgpu_ctx *c, const cgpu_tuples_v4_ct *t, size_t n, uint32_t now, int32_t *verdict,
+			  uint8_t *ct_ret, uint32_t *identity, uint8_t *stage, uint32_t *tunnel, void *stream)
 {
 	Pinned P;
 	if (int r = pin(c, stream, P))
@@ -6099,7 +6378,25 @@ CGPU_EXPORT int cgpu_classify_v4_ct(cgpu_ctx *c, const cgpu_tuples_v4_ct *t, siz
 	a.stage = stage;
 	a.n = n;
 	a.now = now;
+	a.tunnel = tunnel;
+	a.tun = &P.tun();
 	return ct_classify(c, P.snap(), P.delta, c->ct4, a, stream);
+}
+
+CGPU_EXPORT int cgpu_classify_v4_ct(cgpu_ctx *c, const cgpu_tuples_v4_ct *t, size_t n, uint32_t now,
+				    int32_t *verdict, uint8_t *ct_ret, uint32_t *identity,
+				    uint8_t *stage, void *stream)
+{
+	return classify_v4_ct(c, t, n, now, verdict, ct_ret, identity, stage, nullptr, stream);
+}
+
+CGPU_EXPORT int cgpu_classify_v4_ct_tun(cgpu_ctx *c, const cgpu_tuples_v4_ct *t, size_t n, uint32_t now,
+					int32_t *verdict, uint8_t *ct_ret, uint32_t *identity,
+					uint8_t *stage, uint32_t *tunnel, void *stream)
+{
+	if (int r = check_tunnel(c, tunnel))
+		return r;
+	return classify_v4_ct(c, t, n, now, verdict, ct_ret, identity, stage, tunnel, stream);
 }
 
 CGPU_EXPORT int cgpu_classify_v4_ctlb(cgpu_ctx *c, const cgpu_tuples_v4_ct *t, const uint32_t *hash,
@@ -6176,9 +6473,8 @@ CGPU_EXPORT int cgpu_classify_v6_ctlb(cgpu_ctx *c, const cgpu_tuples_v6_ct *t, c
 	return ct_classify(c, P.snap(), P.delta, c->ct6, a, stream, true);
 }
 
-CGPU_EXPORT int cgpu_classify_v6_ct(cgpu_ctx *c, const cgpu_tuples_v6_ct *t, size_t n, uint32_t now,
-				    int32_t *verdict, uint8_t *ct_ret, uint32_t *identity,
-				    uint8_t *stage, void *stream)
+static int classify_v6_ct(cgpu_ctx *c, const cgpu_tuples_v6_ct *t, size_t n, uint32_t now, int32_t *verdict,
+			  uint8_t *ct_ret, uint32_t *identity, uint8_t *stage, uint32_t *tunnel, void *stream)
 {
 	Pinned P;
 	if (int r = pin(c, stream, P))
@@ -6208,7 +6504,25 @@ CGPU_EXPORT int cgpu_classify_v6_ct(cgpu_ctx *c, const cgpu_tuples_v6_ct *t, siz
 	a.stage = stage;
 	a.n = n;
 	a.now = now;
+	a.tunnel = tunnel;
+	a.tun = &P.tun();
 	return ct_classify(c, P.snap(), P.delta, c->ct6, a, stream);
+}
+
+CGPU_EXPORT int cgpu_classify_v6_ct(cgpu_ctx *c, const cgpu_tuples_v6_ct *t, size_t n, uint32_t now,
+				    int32_t *verdict, uint8_t *ct_ret, uint32_t *identity,
+				    uint8_t *stage, void *stream)
+{
+	return classify_v6_ct(c, t, n, now, verdict, ct_ret, identity, stage, nullptr, stream);
+}
+
+CGPU_EXPORT int cgpu_classify_v6_ct_tun(cgpu_ctx *c, const cgpu_tuples_v6_ct *t, size_t n, uint32_t now,
+					int32_t *verdict, uint8_t *ct_ret, uint32_t *identity,
+					uint8_t *stage, uint32_t *tunnel, void *stream)
+{
+	if (int r = check_tunnel(c, tunnel))
+		return r;
+	return classify_v6_ct(c, t, n, now, verdict, ct_ret, identity, stage, tunnel, stream);
 }
 
 /* ======================================================================= */

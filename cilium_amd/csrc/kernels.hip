@@ -1030,28 +1030,52 @@ struct decision {
 	int ctr;
 };
 
-template <int V6>
+/* The tunnel output of a classify kernel (cgpu_classify_v{4,6}_tun): the last
+ * kernel parameter of every instantiation, read only by those with TUN set,
+ * so that the others keep their kernarg offsets and their code.
+ * tunnel[i] = the reference's local tunnel_endpoint behind bpf_lxc.c:488-491
+ * (IPv4) / :177-180 (IPv6): the matched ipcache entry's tunnel_endpoint for an
+ * egress tuple that reached the lookup and matched an entry with sec_label !=
+ * 0, else 0 (ingress, no match, a label-0 match, stages 4 / 6 / 8); whatever
+ * the policy verdict.  Every element is written. */
+struct tun_args {
+	ipc_tun t;
+	uint32_t *tunnel;
+	const uint8_t *proto; /* k_ipc6_pre: the protocol column (stage 4 gate) */
+	uint32_t gate_always; /* k_ipc6_pre: the conntrack paths gate whatever ct_proto_gate says */
+};
+
+/* TUN: *tun = the tuple's tunnel (tun_args); the tunnel table is walked beside
+ * the identity table, not behind it */
+template <int V6, bool TUN = false>
 __device__ __forceinline__ decision decide(const cgpu_snapshot &s, bool egress, bool frag, uint32_t sa4,
 					   uint32_t da4, uint4 sa6, uint4 da6, uint32_t dport, uint32_t proto,
-					   uint32_t ep)
+					   uint32_t ep, const ipc_tun *t = nullptr, uint32_t *tun = nullptr)
 {
 	decision d;
 	const uint32_t eg = egress ? (1u << 24) : 0u;
 	const uint32_t hi4 = dport | (proto << 16) | eg;
 	uint32_t e, label;
+	uint32_t te = 0;
 	bool in_cluster;
 	if (V6) {
 		const uint4 ad = egress ? da6 : sa6;
 		e = v6_lookup(s.ipc6, ad);
+		if (TUN && egress)
+			te = v6_lookup(t->t6, ad);
 		label = entry_label(s.ipc6.vals, e);
 		/* ipv6_match_prefix_64(daddr, ROUTER_IP), bpf/lib/ipv6.h:166-175 */
 		in_cluster = ad.x == s.router_ip64[0] && ad.y == s.router_ip64[1];
 	} else {
 		const uint32_t ad = egress ? da4 : sa4;
 		e = lpmc_lookup(s.ipc4c, s.ipc4c.dict, ad);
+		if (TUN && egress)
+			te = lpmc_lookup(t->t4, t->t4.dict, ad);
 		label = entry_label(s.ipc4c.vals, e);
 		in_cluster = (ad & s.ipv4_cluster_mask) == s.ipv4_cluster_range;
 	}
+	if (TUN)
+		*tun = (egress && e && label) ? entry_label(V6 ? t->t6.vals : t->t4.vals, te) : 0u;
 	if (egress) {
 		if (e && label)
 			d.id = label;
@@ -1235,18 +1259,24 @@ __device__ __forceinline__ void policy_q(const cgpu_snapshot &s, const bool (&ac
  * together, so a wave has Q x 64 independent loads in flight where decide
  * has 64.  Same results as decide<0> tuple by tuple (the stateful path's
  * prep and finish passes; the dictionary is read from global memory). */
-template <int Q>
+/* TUN: tv[u] = the tuple's tunnel (tun_args): the tunnel tables' inline nodes
+ * gathered with the identity's */
+template <int Q, bool TUN = false>
 __device__ __forceinline__ void ident4_q(const cgpu_snapshot &s, const uint32_t *dict, const bool (&act)[Q],
 					 const bool (&eg)[Q], const uint32_t (&sa)[Q], const uint32_t (&da)[Q],
-					 decision (&d)[Q])
+					 decision (&d)[Q], const ipc_tun *tt = nullptr, uint32_t *tv = nullptr)
 {
 	const lpm16c &t = s.ipc4c;
 	uint32_t h[Q], e[Q];
 	uint4 q[Q];
+	uint4 tq[TUN ? Q : 1];
 #pragma unroll
 	for (int u = 0; u < Q; u++) {
 		h[u] = bswap32(eg[u] ? da[u] : sa[u]);
 		q[u] = act[u] ? reinterpret_cast<const uint4 *>(t.x16)[h[u] >> 16] : make_uint4(0, 0, 0, 0);
+		if constexpr (TUN)
+			tq[u] = act[u] && eg[u] ? reinterpret_cast<const uint4 *>(tt->t4.x16)[h[u] >> 16]
+						: make_uint4(0, 0, 0, 0);
 	}
 #pragma unroll
 	for (int u = 0; u < Q; u++) {
@@ -1274,15 +1304,37 @@ __device__ __forceinline__ void ident4_q(const cgpu_snapshot &s, const uint32_t 
 			d[u].id = s.ingress_secctx_world ? s.world_id : src;
 		}
 	}
+	if constexpr (TUN) {
+		uint32_t te[Q];
+#pragma unroll
+		for (int u = 0; u < Q; u++) {
+			te[u] = 0u;
+			if (!act[u] || !eg[u] || (tq[u].w & LPMC_OVERFLOW))
+				continue;
+			const uint32_t x = h[u] & 0xFFFFu;
+			const uint32_t cnt = (x >= (tq[u].x & 0xFFFFu) ? 1u : 0u) + (x >= (tq[u].x >> 16) ? 1u : 0u) +
+					     (x >= (tq[u].y & 0xFFFFu) ? 1u : 0u) + (x >= (tq[u].y >> 16) ? 1u : 0u);
+			const uint64_t v = ((uint64_t)tq[u].w << 32) | tq[u].z;
+			te[u] = tt->t4.dict[(uint32_t)(v >> (12u * cnt)) & 0xFFFu];
+		}
+#pragma unroll
+		for (int u = 0; u < Q; u++) {
+			if (act[u] && eg[u] && (tq[u].w & LPMC_OVERFLOW))
+				te[u] = lpmc_lookup(tt->t4, tt->t4.dict, da[u]);
+			/* bpf_lxc.c:488-491: the match's sec_label != 0 */
+			tv[u] = (act[u] && eg[u] && e[u] && entry_label(t.vals, e[u])) ? entry_label(tt->t4.vals, te[u]) : 0u;
+		}
+	}
 }
 
-template <int Q>
+template <int Q, bool TUN = false>
 __device__ __forceinline__ void decide4_q(const cgpu_snapshot &s, const bool (&act)[Q], const bool (&eg)[Q],
 					  const bool (&frag)[Q], const uint32_t (&sa)[Q], const uint32_t (&da)[Q],
 					  const uint32_t (&dport)[Q], const uint32_t (&proto)[Q],
-					  const uint32_t (&ep)[Q], decision (&d)[Q])
+					  const uint32_t (&ep)[Q], decision (&d)[Q], const ipc_tun *tt = nullptr,
+					  uint32_t *tv = nullptr)
 {
-	ident4_q<Q>(s, s.ipc4c.dict, act, eg, sa, da, d);
+	ident4_q<Q, TUN>(s, s.ipc4c.dict, act, eg, sa, da, d, tt, tv);
 	policy_q<Q>(s, act, eg, frag, dport, proto, ep, d);
 }
 
@@ -1300,8 +1352,8 @@ __device__ __forceinline__ void decide4_q(const cgpu_snapshot &s, const bool (&a
  *          to one packed LDS atomic; the workgroup flushes its LDS counters
  *          to the delta buffer once at the end; cold slots as CTR = 0.
  */
-template <int V6, int CTR, int NT>
-__global__ __launch_bounds__(NT) void k_classify(cgpu_snapshot s, cls_args a)
+template <int V6, int CTR, int NT, bool TUN = false>
+__global__ __launch_bounds__(NT) void k_classify(cgpu_snapshot s, cls_args a, tun_args ta)
 {
 	extern __shared__ __attribute__((aligned(16))) uint64_t lctr[];
 	/* metrics {reason 0 / 133 / 137 / 158} x {ingress, egress} */
@@ -1324,6 +1376,7 @@ __global__ __launch_bounds__(NT) void k_classify(cgpu_snapshot s, cls_args a)
 		int32_t v;
 		uint32_t id;
 		uint32_t st = 0;
+		uint32_t tn = 0; /* TUN: 0 for a tuple that ends before the lookup */
 		/* egress service step (bpf_lxc.c:444-469): ipcache resolves
 		 * tuple.daddr afterwards and policy sees the rewritten dport */
 		bool lbdrop = false;
@@ -1395,7 +1448,7 @@ __global__ __launch_bounds__(NT) void k_classify(cgpu_snapshot s, cls_args a)
 			} else if (!egress) {
 				sa4 = static_cast<const uint32_t *>(a.saddr)[i];
 			}
-			const decision d = decide<V6>(s, egress, frag, sa4, eda, sa6, da6, dport, proto, ep);
+			const decision d = decide<V6, TUN>(s, egress, frag, sa4, eda, sa6, da6, dport, proto, ep, &ta.t, &tn);
 			v = d.v;
 			id = d.id;
 			st = d.st;
@@ -1415,6 +1468,8 @@ __global__ __launch_bounds__(NT) void k_classify(cgpu_snapshot s, cls_args a)
 		a.identity[i] = id;
 		if (a.stage)
 			a.stage[i] = (uint8_t)st;
+		if (TUN)
+			ta.tunnel[i] = tn;
 		/* a proxy redirect (v > 0) traces TRACE_TO_PROXY: no metrics */
 		const uint32_t r = (v > 0 || xdpdrop) ? 4u : v == 0 ? 0u : (v == DROP_POLICY ? 1u : (v == DROP_NO_SERVICE ? 3u : 2u));
 		const uint32_t idx = r * 2u + (egress ? 1u : 0u);
@@ -1763,10 +1818,13 @@ __device__ __forceinline__ uint64_t wave_uniform64(uint64_t x)
  * consecutive slots and each output store 64 consecutive frames), IPv6
  * frames compacted to fx for the v6 pass */
 template <int NT, bool NTL = false, int Q = 4, int MINW = 1, bool LB = false, bool V6 = false,
-	  int FR = 0, bool IPCE = false, bool XDP = false>
-__global__ __launch_bounds__(NT, MINW) void k_classify_x4(cgpu_snapshot s, cls_args a0, uint64_t *pk, frames_x4 fx)
+	  int FR = 0, bool IPCE = false, bool XDP = false, bool TUN = false>
+__global__ __launch_bounds__(NT, MINW) void k_classify_x4(cgpu_snapshot s, cls_args a0, uint64_t *pk, frames_x4 fx,
+							  tun_args ta)
 {
 	constexpr bool FF = FR == 2;
+	/* TUN (tun_args): with the pre-pass (IPCE) k_ipc6_pre writes the tunnels */
+	static_assert(!TUN || (FR == 0 && !IPCE), "the tunnel output: tuple columns, lookups in this kernel");
 	static_assert(!XDP || (LB && !V6), "the XDP prefilter: the IPv4 cascade");
 	static_assert(!FF || (Q == 4 && !V6 && !LB), "fused frames: the v4 x4 schedule");
 	cls_args a = a0;
@@ -2191,6 +2249,17 @@ __global__ __launch_bounds__(NT, MINW) void k_classify_x4(cgpu_snapshot s, cls_a
 		}
 		/* ipcache lookup (eps.h:56-80) */
 		uint32_t e[Q];
+		/* TUN: the tunnel leaves of the egress tuples that reach the lookup,
+		 * their gathers issued with the identity's (tables.h ipc_tun) */
+		uint32_t te[TUN ? Q : 1];
+		bool twant[TUN ? Q : 1];
+		if constexpr (TUN) {
+#pragma unroll
+			for (int u = 0; u < Q; u++) {
+				te[u] = 0u;
+				twant[u] = (fw[u] & (F_OK | F_GATED | F_LBDROP | F_EG)) == (F_OK | F_EG);
+			}
+		}
 		if (V6) {
 			bool act[Q];
 #pragma unroll
@@ -2218,6 +2287,14 @@ __global__ __launch_bounds__(NT, MINW) void k_classify_x4(cgpu_snapshot s, cls_a
 				for (int u = 0; u < Q; u++)
 					e[u] = act[u] ? pe[u] : 0u;
 			} else {
+				if constexpr (TUN) {
+					/* Q independent walks of the tunnel trie from device
+					 * memory, ahead of the identity's staged walk */
+#pragma unroll
+					for (int u = 0; u < Q; u++)
+						if (twant[u])
+							te[u] = v6_lookup(ta.t.t6, v6_host_words(ad6[u]));
+				}
 				v6t_lookup_q<Q>(s.ipc6, ldict, n24 != 0u, ad6, act, e);
 			}
 #endif
@@ -2226,11 +2303,36 @@ __global__ __launch_bounds__(NT, MINW) void k_classify_x4(cgpu_snapshot s, cls_a
 			{
 				/* one 16-byte gather: the /16's inline run node (tables.h) */
 				uint4 q[Q];
+				uint4 tq[TUN ? Q : 1];
 #pragma unroll
 				for (int u = 0; u < Q; u++) {
 					q[u] = make_uint4(0, 0, 0, 0);
 					if ((fw[u] & (F_OK | F_GATED | F_LBDROP)) == F_OK)
 						q[u] = reinterpret_cast<const uint4 *>(s.ipc4c.x16)[DIAG_LPM(bswap32(ad[u]) >> 16)];
+					if constexpr (TUN) {
+						tq[u] = make_uint4(0, 0, 0, 0);
+						if (twant[u])
+							tq[u] = reinterpret_cast<const uint4 *>(ta.t.t4.x16)[bswap32(ad[u]) >> 16];
+					}
+				}
+				if constexpr (TUN) {
+					/* the inline node's leaf from the dictionary in device
+					 * memory (no LDS copy: the LDS is the counters'), all
+					 * Q together; an overflowing /16 walks the compressed LPM */
+#pragma unroll
+					for (int u = 0; u < Q; u++) {
+						if (!twant[u] || (tq[u].w & LPMC_OVERFLOW))
+							continue;
+						const uint32_t x = bswap32(ad[u]) & 0xFFFFu;
+						const uint32_t cnt = (x >= (tq[u].x & 0xFFFFu) ? 1u : 0u) + (x >= (tq[u].x >> 16) ? 1u : 0u) +
+								     (x >= (tq[u].y & 0xFFFFu) ? 1u : 0u) + (x >= (tq[u].y >> 16) ? 1u : 0u);
+						const uint64_t v = ((uint64_t)tq[u].w << 32) | tq[u].z;
+						te[u] = ta.t.t4.dict[(uint32_t)(v >> (12u * cnt)) & 0xFFFu];
+					}
+#pragma unroll
+					for (int u = 0; u < Q; u++)
+						if (twant[u] && (tq[u].w & LPMC_OVERFLOW))
+							te[u] = lpmc_lookup(ta.t.t4, ta.t.t4.dict, ad[u]);
 				}
 #pragma unroll
 				for (int u = 0; u < Q; u++) {
@@ -2293,9 +2395,12 @@ __global__ __launch_bounds__(NT, MINW) void k_classify_x4(cgpu_snapshot s, cls_a
 		}
 		/* identity (bpf_lxc.c:488-496 / bpf_netdev.c:374-404) */
 		uint32_t id[QA];
+		uint32_t tv[TUN ? QA : 1];
 #pragma unroll
 		for (int u = 0; u < Q; u++) {
 			const uint32_t label = entry_label(V6 ? s.ipc6.vals : s.ipc4c.vals, e[u]);
+			if constexpr (TUN) /* bpf_lxc.c:488-491 / :177-180: sec_label != 0 */
+				tv[u] = (twant[u] && e[u] && label) ? entry_label(V6 ? ta.t.t6.vals : ta.t.t4.vals, te[u]) : 0u;
 			/* v6: ipv6_match_prefix_64(daddr, ROUTER_IP), bpf/lib/ipv6.h:166-175
 			 * (ad6: host-order words) */
 			const bool in_cluster = V6 ? ad6[u].x == bswap32(s.router_ip64[0]) &&
@@ -2514,11 +2619,15 @@ __global__ __launch_bounds__(NT, MINW) void k_classify_x4(cgpu_snapshot s, cls_a
 #endif
 			if (a.stage)
 				st_x1<NTL>(a.stage + i0, st[0] | (st[1] << 8) | (st[2] << 16) | (st[3] << 24));
+			if constexpr (TUN)
+				st_x4<NTL>(ta.tunnel + i0, tv[0], tv[1], tv[2], tv[3]);
 		} else if (full && Q == 2) {
 			*reinterpret_cast<int2 *>(a.verdict + i0) = make_int2(v[0], v[1]);
 			*reinterpret_cast<uint2 *>(a.identity + i0) = make_uint2(id[0], id[1]);
 			if (a.stage)
 				*reinterpret_cast<uint16_t *>(a.stage + i0) = (uint16_t)(st[0] | (st[1] << 8));
+			if constexpr (TUN)
+				*reinterpret_cast<uint2 *>(ta.tunnel + i0) = make_uint2(tv[0], tv[1]);
 		} else {
 #pragma unroll
 			for (int u = 0; u < Q; u++)
@@ -2527,6 +2636,8 @@ __global__ __launch_bounds__(NT, MINW) void k_classify_x4(cgpu_snapshot s, cls_a
 					a.identity[i0 + u] = id[u];
 					if (a.stage)
 						a.stage[i0 + u] = (uint8_t)st[u];
+					if constexpr (TUN)
+						ta.tunnel[i0 + u] = tv[u];
 				}
 		}
 	}
@@ -3324,6 +3435,63 @@ __global__ __launch_bounds__(256) void k_table_sum(const uint64_t *buf, uint64_t
 		atomicAdd((unsigned long long *)out, (unsigned long long)acc);
 }
 
+/* 16 address bytes at any alignment, as the four little-endian words a
+ * 16-byte load gives; al: the column base's alignment class (uniform) */
+__device__ __forceinline__ uint4 ld_addr16(const uint8_t *p, uint32_t al)
+{
+	if (al == 0)
+		return *reinterpret_cast<const uint4 *>(p);
+	if (al == 1) {
+		const uint32_t *w = reinterpret_cast<const uint32_t *>(p);
+		return make_uint4(w[0], w[1], w[2], w[3]);
+	}
+	uint32_t w[4];
+#pragma unroll
+	for (int k = 0; k < 4; k++)
+		w[k] = (uint32_t)p[4 * k] | (uint32_t)p[4 * k + 1] << 8 | (uint32_t)p[4 * k + 2] << 16 |
+		       (uint32_t)p[4 * k + 3] << 24;
+	return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+/* Batched ipcache lookup (cgpu_ipcache_lookup_v4 / _v6): ipcache_lookup4 /
+ * ipcache_lookup6 themselves (bpf/lib/eps.h:56-80), one address per lane,
+ * grid-stride.  The identity table says whether an entry matched (a
+ * tombstone is a match); the tunnel table (tables.h ipc_tun) is walked
+ * beside it, not behind it, so the two chains of gathers overlap, and its
+ * leaf counts only under a match.  TUN = false reads no tunnel table. */
+template <bool V6, bool TUN>
+__global__ __launch_bounds__(BLOCK) void k_ipcache_lookup(lpm16c id4, v6_lpm id6, ipc_tun t, ipc_lookup_args a)
+{
+	const uint64_t stride = (uint64_t)gridDim.x * BLOCK;
+	const uint32_t al = ((uintptr_t)a.addr & 15u) == 0 ? 0u : (((uintptr_t)a.addr & 3u) == 0 ? 1u : 2u);
+	for (uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i < a.n; i += stride) {
+		uint32_t e, te = 0, lab, tv = 0;
+		if (V6) {
+			const uint4 x = ld_addr16(static_cast<const uint8_t *>(a.addr) + 16u * i, al);
+			e = v6_lookup(id6, x);
+			if (TUN)
+				te = v6_lookup(t.t6, x);
+			lab = entry_label(id6.vals, e);
+			if (TUN)
+				tv = entry_label(t.t6.vals, te);
+		} else {
+			const uint32_t x = static_cast<const uint32_t *>(a.addr)[i];
+			e = lpmc_lookup(id4, id4.dict, x);
+			if (TUN)
+				te = lpmc_lookup(t.t4, t.t4.dict, x);
+			lab = entry_label(id4.vals, e);
+			if (TUN)
+				tv = entry_label(t.t4.vals, te);
+		}
+		if (a.found)
+			a.found[i] = e != 0u;
+		if (a.label)
+			a.label[i] = lab;
+		if (TUN)
+			a.tunnel[i] = e ? tv : 0u;
+	}
+}
+
 unsigned grid_for(uint64_t n)
 {
 	uint64_t blocks = (n + BLOCK - 1) / BLOCK;
@@ -3419,10 +3587,14 @@ static cgpu_snapshot with_lds_hot(const cgpu_snapshot &s, size_t max_hot)
 #define SVC_XLATED 1u
 #define SVC_DROP 2u
 
-template <int Q, int NT>
+/* TUN (tun_args): this pass reads the addresses and the classify kernel
+ * behind it does not, so the tunnel output is resolved and written here,
+ * whole: the tunnel trie walked per lane ahead of the identity's staged walk,
+ * gated by the protocol (stage 4) and by the identity match's sec_label */
+template <int Q, int NT, bool TUN = false>
 __global__ __launch_bounds__(NT, CGPU_IPC6_MINW) void k_ipc6_pre(cgpu_snapshot s, const uint4 *sa, const uint4 *da,
 						 const uint8_t *flags, uint32_t *e_out, uint64_t n,
-						 const uint4 *svc)
+						 const uint4 *svc, tun_args ta)
 {
 	/* svc (the IPv6 service path, or NULL): an egress packet lb6_local
 	 * translated is looked up on its target (svc[2i + 1]) */
@@ -3486,12 +3658,32 @@ __global__ __launch_bounds__(NT, CGPU_IPC6_MINW) void k_ipc6_pre(cgpu_snapshot s
 			}
 		}
 #endif
+		uint32_t te[TUN ? Q : 1];
+		bool twant[TUN ? Q : 1];
+		if constexpr (TUN) {
+#pragma unroll
+			for (int u = 0; u < Q; u++) {
+				te[u] = 0u;
+				twant[u] = false;
+				if (!act[u] || !eg[u])
+					continue;
+				const uint32_t pr = ta.proto[g + (uint64_t)u * T];
+				/* a gated protocol ends before the lookup (stage 4) */
+				twant[u] = !((s.ct_proto_gate || ta.gate_always) && pr != 58u && pr != 6u && pr != 17u);
+				if (twant[u])
+					te[u] = v6_lookup(ta.t.t6, v6_host_words(w[u]));
+			}
+		}
 		v6t_lookup_q<Q>(s.ipc6, lt, n24 != 0u, w, act, e, nbl ? lbl : nullptr);
 #pragma unroll
 		for (int u = 0; u < Q; u++) {
 			const uint64_t i = g + (uint64_t)u * T;
 			if (!act[u])
 				continue;
+			if constexpr (TUN) /* e[u]: the match itself, before the fallback is folded in */
+				ta.tunnel[i] = (twant[u] && e[u] && entry_label(s.ipc6.vals, e[u]))
+						       ? entry_label(ta.t.t6.vals, te[u])
+						       : 0u;
 			/* the classify kernel reads no address: an egress tuple's
 			 * fallback identity (no match or a label-0 match) is folded in
 			 * here, as a DIRECT entry of cluster_id when the address lies in
@@ -3512,14 +3704,24 @@ __global__ __launch_bounds__(NT, CGPU_IPC6_MINW) void k_ipc6_pre(cgpu_snapshot s
 #define CGPU_DIAG_IPC6_PRE_Q 2
 #endif
 
-static hipError_t launch_ipc6_pre(const cgpu_snapshot &s, const cls_args &a, hipStream_t st)
+static hipError_t launch_ipc6_pre(const cgpu_snapshot &s, const cls_args &a, hipStream_t st,
+				  const tun_args &ta = tun_args{})
 {
 	constexpr int NT = 1024, Q = CGPU_DIAG_IPC6_PRE_Q;
 	const size_t lds = (size_t)(v6t_lds_words(s.ipc6) + v6t_lds_bloom(s.ipc6)) * 4u;
-	const unsigned res = resident_blocks((const void *)k_ipc6_pre<Q, NT>, NT, lds);
+	const void *kern = ta.tunnel ? (const void *)k_ipc6_pre<Q, NT, true> : (const void *)k_ipc6_pre<Q, NT>;
+	const unsigned res = resident_blocks(kern, NT, lds);
 	const unsigned g = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((a.n + Q * NT - 1) / (Q * NT), res));
-	hipLaunchKernelGGL((k_ipc6_pre<Q, NT>), dim3(g), dim3(NT), lds, st, s, static_cast<const uint4 *>(a.saddr),
-			   static_cast<const uint4 *>(a.daddr), a.flags, a.ipc_e, a.n, nullptr);
+	if (ta.tunnel) {
+		tun_args t = ta;
+		t.proto = a.proto;
+		hipLaunchKernelGGL((k_ipc6_pre<Q, NT, true>), dim3(g), dim3(NT), lds, st, s,
+				   static_cast<const uint4 *>(a.saddr), static_cast<const uint4 *>(a.daddr), a.flags, a.ipc_e,
+				   a.n, nullptr, t);
+	} else {
+		hipLaunchKernelGGL((k_ipc6_pre<Q, NT>), dim3(g), dim3(NT), lds, st, s, static_cast<const uint4 *>(a.saddr),
+				   static_cast<const uint4 *>(a.daddr), a.flags, a.ipc_e, a.n, nullptr, ta);
+	}
 	return hipGetLastError();
 }
 
@@ -3530,14 +3732,17 @@ static hipError_t launch_ipc6_pre(const cgpu_snapshot &s, const cls_args &a, hip
 #ifndef CGPU_XDP_Q
 #define CGPU_XDP_Q 2
 #endif
-template <bool LB, bool V6, int FR = 0, bool IPCE = false, bool XDP = false>
+/* TUN: the tunnel output (tun_args; ta.tunnel set).  With the pre-pass (IPCE)
+ * k_ipc6_pre writes it and the classify kernel is the one without it. */
+template <bool LB, bool V6, int FR = 0, bool IPCE = false, bool XDP = false, bool TUN = false>
 static hipError_t launch_x4(const cgpu_snapshot &s0, const cls_args &a, hipStream_t st,
-			    const frames_x4 &fx = frames_x4{})
+			    const frames_x4 &fx = frames_x4{}, const tun_args &ta = tun_args{})
 {
 	constexpr bool FF = FR == 2;
 	constexpr int NT = 1024;
+	constexpr bool KTUN = TUN && !IPCE; /* the classify kernel itself writes tunnels */
 	if constexpr (IPCE) {
-		hipError_t e = launch_ipc6_pre(s0, a, st);
+		hipError_t e = launch_ipc6_pre(s0, a, st, TUN ? ta : tun_args{});
 		if (e != hipSuccess)
 			return e;
 	}
@@ -3565,7 +3770,7 @@ static hipError_t launch_x4(const cgpu_snapshot &s0, const cls_args &a, hipStrea
 #else
 	constexpr int Q = V6 && !IPCE ? 2 : XDP ? CGPU_XDP_Q : 4; /* in-kernel v6 lookups: the trie's line registers */
 #endif
-	const void *kern = (const void *)k_classify_x4<NT, true, Q, 1, LB, V6, FR, IPCE, XDP>;
+	const void *kern = (const void *)k_classify_x4<NT, true, Q, 1, LB, V6, FR, IPCE, XDP, KTUN>;
 	static_assert(!FF || Q == 4, "fused frames: Q = 4");
 	const unsigned res = resident_blocks(kern, NT, lds);
 	/* LDS packed counters: <= 2^22 tuples per workgroup (PK_SHIFT) */
@@ -3597,9 +3802,12 @@ static hipError_t launch_x4(const cgpu_snapshot &s0, const cls_args &a, hipStrea
 		if (c.ipc_e)
 			c.ipc_e += off;
 		c.n_off = off;
+		tun_args tc = KTUN ? ta : tun_args{};
+		if (KTUN)
+			tc.tunnel += off;
 		const unsigned g = (unsigned)std::min<uint64_t>((m + Q * NT - 1) / (Q * NT), res);
-		hipLaunchKernelGGL((k_classify_x4<NT, true, Q, 1, LB, V6, FR, IPCE, XDP>), dim3(g), dim3(NT), lds, st, s, c,
-				   a.pk, fx);
+		hipLaunchKernelGGL((k_classify_x4<NT, true, Q, 1, LB, V6, FR, IPCE, XDP, KTUN>), dim3(g), dim3(NT), lds, st, s,
+				   c, a.pk, fx, tc);
 		if (s.cold_hi) {
 			const unsigned ug = std::min<unsigned>((s.cold_hi + 255) / 256, 1024);
 			hipLaunchKernelGGL(k_unpack, dim3(ug), dim3(256), 0, st, a.delta, a.pk, 0u, s.cold_hi);
@@ -3615,20 +3823,25 @@ static hipError_t launch_x4(const cgpu_snapshot &s0, const cls_args &a, hipStrea
  *      aligned columns, else the per-lane kernel)
  *   CGPU_SCHED_PER_LANE: one tuple per lane, LDS hot counters
  *   CGPU_SCHED_GLOBAL_CTR: global atomics for every hit, 256-thread workgroups */
-template <int V6>
-static hipError_t launch_classify(const cgpu_snapshot &s0, cls_args a, hipStream_t st)
+template <int V6, bool TUN = false>
+static hipError_t launch_classify(const cgpu_snapshot &s0, cls_args a, hipStream_t st,
+				  const tun_args &ta = tun_args{})
 {
 	if (s0.schedule & CGPU_SCHED_GLOBAL_CTR) {
-		hipLaunchKernelGGL((k_classify<V6, 0, BLOCK>), dim3(grid_for(a.n)), dim3(BLOCK), 0, st, s0, a);
+		hipLaunchKernelGGL((k_classify<V6, 0, BLOCK, TUN>), dim3(grid_for(a.n)), dim3(BLOCK), 0, st, s0, a, ta);
 		return hipGetLastError();
 	}
-	if (!(s0.schedule & CGPU_SCHED_PER_LANE) && a.pk && x4_aligned(a)) {
+	/* (the x4 kernels store four tunnels as one 16-byte vector) */
+	if (!(s0.schedule & CGPU_SCHED_PER_LANE) && a.pk && x4_aligned(a) && !((uintptr_t)ta.tunnel & 15)) {
+		const frames_x4 nofx{};
 		if (V6)
-			return a.lb ? launch_x4<true, true>(s0, a, st)
-				    : (a.ipc_e ? launch_x4<false, true, false, true>(s0, a, st) : launch_x4<false, true>(s0, a, st));
+			return a.lb ? launch_x4<true, true, 0, false, false, TUN>(s0, a, st, nofx, ta)
+				    : (a.ipc_e ? launch_x4<false, true, 0, true, false, TUN>(s0, a, st, nofx, ta)
+					       : launch_x4<false, true, 0, false, false, TUN>(s0, a, st, nofx, ta));
 		if (a.lb)
-			return a.xdp ? launch_x4<true, false, 0, false, true>(s0, a, st) : launch_x4<true, false>(s0, a, st);
-		return launch_x4<false, false>(s0, a, st);
+			return a.xdp ? launch_x4<true, false, 0, false, true, TUN>(s0, a, st, nofx, ta)
+				     : launch_x4<true, false, 0, false, false, TUN>(s0, a, st, nofx, ta);
+		return launch_x4<false, false, 0, false, false, TUN>(s0, a, st, nofx, ta);
 	}
 	/* LDS counters: 1024-thread workgroups, <= 2 per CU (LDS), and at most
 	 * 2^22 tuples per workgroup (packed-counter exactness) */
@@ -3656,8 +3869,11 @@ static hipError_t launch_classify(const cgpu_snapshot &s0, cls_args a, hipStream
 			c.sport += off;
 		if (c.hash)
 			c.hash += off;
+		tun_args tc = ta;
+		if (TUN)
+			tc.tunnel += off;
 		const unsigned g = (unsigned)std::min<uint64_t>((m + NT - 1) / NT, cap);
-		hipLaunchKernelGGL((k_classify<V6, 1, NT>), dim3(g), dim3(NT), lds, st, s, c);
+		hipLaunchKernelGGL((k_classify<V6, 1, NT, TUN>), dim3(g), dim3(NT), lds, st, s, c, tc);
 	}
 	return hipGetLastError();
 }
@@ -3667,6 +3883,8 @@ hipError_t launch_classify_v4(const cgpu_snapshot &s, const classify_v4_args &x,
 	cls_args c{x.saddr, x.daddr, x.dport, x.proto, x.flags, x.len, x.ep, x.verdict, x.identity,
 		   x.stage, x.delta, x.n, x.pk, x.lb, x.sport, x.hash};
 	c.xdp = x.lb ? x.xdp : 0;
+	if (x.tunnel)
+		return launch_classify<0, true>(s, c, st, tun_args{*x.tun, x.tunnel, nullptr});
 	return launch_classify<0>(s, c, st);
 }
 
@@ -3675,6 +3893,8 @@ hipError_t launch_classify_v6(const cgpu_snapshot &s, const classify_v6_args &x,
 	cls_args c{x.saddr16, x.daddr16, x.dport, x.proto, x.flags, x.len, x.ep, x.verdict, x.identity,
 		   x.stage, x.delta, x.n, x.pk, x.lb, x.sport, x.hash};
 	c.ipc_e = x.ipc_e;
+	if (x.tunnel)
+		return launch_classify<1, true>(s, c, st, tun_args{*x.tun, x.tunnel, nullptr});
 	return launch_classify<1>(s, c, st);
 }
 
@@ -3684,6 +3904,26 @@ hipError_t launch_lb4(const cgpu_snapshot &s, const lb4_args &a, hipStream_t st)
 		hipLaunchKernelGGL(k_lb4<CGPU_LB_NETDEV>, dim3(grid_for(a.n)), dim3(BLOCK), 0, st, s, a);
 	else
 		hipLaunchKernelGGL(k_lb4<CGPU_LB_LXC>, dim3(grid_for(a.n)), dim3(BLOCK), 0, st, s, a);
+	return hipGetLastError();
+}
+
+hipError_t launch_ipcache_lookup(const cgpu_snapshot &s, const ipc_tun &t, const ipc_lookup_args &a,
+				 hipStream_t st)
+{
+	if (!a.n)
+		return hipSuccess;
+	const dim3 g(grid_for(a.n)), b(BLOCK);
+	if (a.v6) {
+		if (a.tunnel)
+			hipLaunchKernelGGL((k_ipcache_lookup<true, true>), g, b, 0, st, s.ipc4c, s.ipc6, t, a);
+		else
+			hipLaunchKernelGGL((k_ipcache_lookup<true, false>), g, b, 0, st, s.ipc4c, s.ipc6, t, a);
+	} else {
+		if (a.tunnel)
+			hipLaunchKernelGGL((k_ipcache_lookup<false, true>), g, b, 0, st, s.ipc4c, s.ipc6, t, a);
+		else
+			hipLaunchKernelGGL((k_ipcache_lookup<false, false>), g, b, 0, st, s.ipc4c, s.ipc6, t, a);
+	}
 	return hipGetLastError();
 }
 
@@ -5203,8 +5443,10 @@ __global__ __launch_bounds__(256) void k_ct_prep_svc_q(cgpu_snapshot s, ct_args 
 /* k_ct_prep<false, false> (the plain IPv4 path) with Q packets per lane:
  * the forward decisions through decide4_q; packet i = g + u * (threads),
  * so every column load of a wave covers 64 consecutive packets */
-template <int Q>
-__global__ __launch_bounds__(256) void k_ct_prep_q(cgpu_snapshot s, ct_args a)
+/* TUN (tun_args): the forward tuple's tunnel; a packet whose ct_lookup fails
+ * (an unknown protocol, ct_ret CGPU_CT_NONE) never reaches the lookup: 0 */
+template <int Q, bool TUN = false>
+__global__ __launch_bounds__(256) void k_ct_prep_q(cgpu_snapshot s, ct_args a, tun_args ta)
 {
 	const uint64_t T = (uint64_t)gridDim.x * 256u;
 	for (uint64_t g = (uint64_t)blockIdx.x * 256u + threadIdx.x; g < a.n; g += T * Q) {
@@ -5256,12 +5498,15 @@ __global__ __launch_bounds__(256) void k_ct_prep_q(cgpu_snapshot s, ct_args a)
 			fdp[u] = z[u] >> 16;
 		}
 		decision d[Q];
-		decide4_q<Q>(s, dec, eg, frag, sa, da, fdp, pr, ep, d);
+		uint32_t tv[TUN ? Q : 1];
+		decide4_q<Q, TUN>(s, dec, eg, frag, sa, da, fdp, pr, ep, d, &ta.t, tv);
 #pragma unroll
 		for (int u = 0; u < Q; u++) {
 			if (!act[u])
 				continue;
 			const uint64_t i = g + (uint64_t)u * T;
+			if constexpr (TUN)
+				ta.tunnel[i] = tv[u]; /* 0 unless dec[u] (ident4_q's act) */
 			uint32_t sec = 0, port = 0, cst = 0, id = 0, m = meta[u];
 			if (dec[u]) {
 				if (d[u].v >= 0) {
@@ -5676,9 +5921,10 @@ __global__ __launch_bounds__(256) void k_ct_heads(const uint32_t *g, uint8_t *he
  * decision, as k_ct_prep; IPv6 has no fragment flag (bpf_lxc.c:787-789) and
  * an ingress entry carries the reverse NAT index ipv6_policy derives from
  * the destination address, daddr.s6_addr32[3] & 0xFFFF (bpf_lxc.c:748). */
-template <bool SVC>
-__global__ __launch_bounds__(256) void k_ct_prep6(cgpu_snapshot s, ct_args a)
+template <bool SVC, bool TUN = false>
+__global__ __launch_bounds__(256) void k_ct_prep6(cgpu_snapshot s, ct_args a, tun_args ta)
 {
+	static_assert(!TUN || !SVC, "the tunnel output: the plain conntrack path");
 	const uint64_t stride = (uint64_t)gridDim.x * 256u;
 	const uint4 *sa16 = reinterpret_cast<const uint4 *>(a.saddr);
 	const uint4 *da16 = reinterpret_cast<const uint4 *>(a.daddr);
@@ -5745,11 +5991,12 @@ __global__ __launch_bounds__(256) void k_ct_prep6(cgpu_snapshot s, ct_args a)
 		if (pr != 6u)
 			w = 0; /* union tcp_flags stays zero (conntrack.h:294) */
 		uint32_t sec = 0, port = 0, cst = 0, id = 0;
+		uint32_t tn = 0; /* TUN: 0 for a gated packet (ct_ret CGPU_CT_NONE) */
 		if (!(meta & CTM_GATED)) {
 			if (egress)
 				sec = ep < s.n_lxc ? s.lxc[2u * ep + 1u].w : 0u; /* SECLABEL */
 			if constexpr (!SVC || !CGPU_CT_SVC_DECQ6) {
-				const decision d = decide<1>(s, egress, false, 0u, 0u, sa, da, z >> 16, pr, ep);
+				const decision d = decide<1, TUN>(s, egress, false, 0u, 0u, sa, da, z >> 16, pr, ep, &ta.t, &tn);
 				if (d.v >= 0) {
 					meta |= CTM_ALLOWED;
 					port = (uint32_t)d.v;
@@ -5776,6 +6023,8 @@ __global__ __launch_bounds__(256) void k_ct_prep6(cgpu_snapshot s, ct_args a)
 			reinterpret_cast<uint16_t *>(a.f2)[i] = p2 ? 1u : 0u;
 		}
 		a.identity[i] = id;
+		if constexpr (TUN)
+			ta.tunnel[i] = tn;
 		uint4 *r = a.rec + 4u * i;
 		r[0] = da;
 		r[1] = sa;
@@ -7475,24 +7724,38 @@ static hipError_t launch_ct(const cgpu_snapshot &s, const ct_table &T, const ct_
 	if (!CGPU_CT_DFLT || (K::V6 && !pre6))
 		a.dflt = 0u;
 	const unsigned g = (unsigned)std::min<uint64_t>((L.n + 255) / 256, 8192);
+	/* cgpu_classify_v{4,6}_ct_tun: the preps write the forward tuple's tunnel
+	 * (IPv6 with the pre-pass: the pre-pass does, it reads the addresses) */
+	const tun_args ta = L.tunnel ? tun_args{*L.tun, L.tunnel, L.proto, 1u} : tun_args{};
 	if (K::V6) {
 		if (pre6) {
 			constexpr int NT = 1024, QP = CGPU_DIAG_IPC6_PRE_Q, Q = 4;
 			const size_t lds = (size_t)(v6t_lds_words(s.ipc6) + v6t_lds_bloom(s.ipc6)) * 4u;
-			const unsigned res = resident_blocks((const void *)k_ipc6_pre<QP, NT>, NT, lds);
+			const void *kern = L.tunnel ? (const void *)k_ipc6_pre<QP, NT, true> : (const void *)k_ipc6_pre<QP, NT>;
+			const unsigned res = resident_blocks(kern, NT, lds);
 			const unsigned gp = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((L.n + QP * NT - 1) / (QP * NT), res));
-			hipLaunchKernelGGL((k_ipc6_pre<QP, NT>), dim3(gp), dim3(NT), lds, st, s,
-					   static_cast<const uint4 *>(L.saddr), static_cast<const uint4 *>(L.daddr), L.flags,
-					   L.idx_sorted, L.n, nullptr);
+			if (L.tunnel)
+				hipLaunchKernelGGL((k_ipc6_pre<QP, NT, true>), dim3(gp), dim3(NT), lds, st, s,
+						   static_cast<const uint4 *>(L.saddr), static_cast<const uint4 *>(L.daddr),
+						   L.flags, L.idx_sorted, L.n, nullptr, ta);
+			else
+				hipLaunchKernelGGL((k_ipc6_pre<QP, NT>), dim3(gp), dim3(NT), lds, st, s,
+						   static_cast<const uint4 *>(L.saddr), static_cast<const uint4 *>(L.daddr),
+						   L.flags, L.idx_sorted, L.n, nullptr, ta);
 			const unsigned gq = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((L.n + 256 * Q - 1) / (256 * Q), 8192));
 			hipLaunchKernelGGL((k_ct_prep6_q<Q>), dim3(gq), dim3(256), 0, st, s, a, L.idx_sorted);
+		} else if (L.tunnel) {
+			hipLaunchKernelGGL((k_ct_prep6<false, true>), dim3(g), dim3(256), 0, st, s, a, ta);
 		} else {
-			hipLaunchKernelGGL(k_ct_prep6<false>, dim3(g), dim3(256), 0, st, s, a);
+			hipLaunchKernelGGL(k_ct_prep6<false>, dim3(g), dim3(256), 0, st, s, a, ta);
 		}
 	} else {
 		constexpr int Q = CGPU_CT_Q;
 		const unsigned gq = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((L.n + 256 * Q - 1) / (256 * Q), 8192));
-		hipLaunchKernelGGL((k_ct_prep_q<Q>), dim3(gq), dim3(256), 0, st, s, a);
+		if (L.tunnel)
+			hipLaunchKernelGGL((k_ct_prep_q<Q, true>), dim3(gq), dim3(256), 0, st, s, a, ta);
+		else
+			hipLaunchKernelGGL((k_ct_prep_q<Q>), dim3(gq), dim3(256), 0, st, s, a, ta);
 	}
 	if (T.lru) {
 		/* LRU mode: every key the batch can touch into the filter the
@@ -7575,12 +7838,12 @@ hipError_t launch_classify_v6_ctlb(const cgpu_snapshot &s, const ct_table &T, co
 		const unsigned gp = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((L.n + QP * NT - 1) / (QP * NT), res));
 		hipLaunchKernelGGL((k_ipc6_pre<QP, NT>), dim3(gp), dim3(NT), lds, st, s,
 				   static_cast<const uint4 *>(L.saddr), static_cast<const uint4 *>(L.daddr), L.flags,
-				   L.idx_sorted, L.n, static_cast<const uint4 *>(a.svc_out));
+				   L.idx_sorted, L.n, static_cast<const uint4 *>(a.svc_out), tun_args{});
 		const unsigned gq = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((L.n + 256 * Q - 1) / (256 * Q), 8192));
 		hipLaunchKernelGGL((k_ct_prep6_q<Q, true>), dim3(gq), dim3(256), 0, st, s, a, L.idx_sorted);
 	} else {
 		a.dflt = 0u; /* k_ct_prep6 stores every result */
-		hipLaunchKernelGGL(k_ct_prep6<true>, dim3(g), dim3(256), 0, st, s, a);
+		hipLaunchKernelGGL(k_ct_prep6<true>, dim3(g), dim3(256), 0, st, s, a, tun_args{});
 		launch_ct_decq<CtK6S>(s, a, st);
 	}
 	e = ct_group_sort(s, L, a, L.n, &nh, st, true);

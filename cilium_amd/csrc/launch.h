@@ -28,6 +28,10 @@ struct classify_v4_args {
 	const uint32_t *hash; /* NULL: flow_hash(saddr, daddr, sport, dport, proto) */
 	/* with lb: the XDP prefilter before every ingress tuple (cgpu_classify_v4_cascade) */
 	int xdp;
+	/* cgpu_classify_v4_tun: [n] tunnel endpoints out (NULL: none) from the
+	 * tunnel tables `tun` */
+	uint32_t *tunnel;
+	const ipc_tun *tun;
 };
 
 hipError_t launch_classify_v4(const cgpu_snapshot &s, const classify_v4_args &a, hipStream_t st);
@@ -51,9 +55,25 @@ struct classify_v6_args {
 	/* scratch of n u32 (optional): the x4 schedule's ipcache pre-pass
 	 * (k_ipc6_pre) writes every tuple's trie entry there */
 	uint32_t *ipc_e;
+	/* cgpu_classify_v6_tun: as classify_v4_args */
+	uint32_t *tunnel;
+	const ipc_tun *tun;
 };
 
 hipError_t launch_classify_v6(const cgpu_snapshot &s, const classify_v6_args &a, hipStream_t st);
+
+/* batched ipcache lookup (cgpu_ipcache_lookup_v4 / _v6): any output may be
+ * NULL; tunnel only with the tunnel tables compiled (t.t4.d16) */
+struct ipc_lookup_args {
+	const void *addr; /* u32 per address (v4); 16 bytes, any alignment (v6) */
+	uint64_t n;
+	uint8_t *found;
+	uint32_t *label, *tunnel;
+	int v6;
+};
+
+hipError_t launch_ipcache_lookup(const cgpu_snapshot &s, const ipc_tun &t, const ipc_lookup_args &a,
+				 hipStream_t st);
 
 struct prefilter_args {
 	const uint32_t *saddr4, *daddr4;
@@ -162,6 +182,10 @@ struct ct_launch {
 	void *xdaddr;         /* [n] optional (IPv6: 16 bytes each) */
 	uint16_t *xdport;     /* [n] optional */
 	uint32_t dflt;        /* nonzero: group-default results (CGPU_CT_DFLT) */
+	/* cgpu_classify_v{4,6}_ct_tun: [n] tunnel endpoints out (NULL: none) from
+	 * the tunnel tables `tun` (plain paths only) */
+	uint32_t *tunnel;
+	const ipc_tun *tun;
 };
 
 size_t ct_temp_bytes(uint64_t n);

@@ -490,6 +490,22 @@ typedef struct cgpu_snapshot {
 	uint64_t epoch;
 } cgpu_snapshot;
 
+/* ---- ipcache tunnel endpoints (cgpu_config.ipcache_tunnel) ----
+ * The second word of the ipcache value, struct remote_endpoint_info
+ * {sec_label, tunnel_endpoint} (bpf/lib/common.h:175-178): a second instance
+ * of each compiled ipcache LPM, built from the same candidates in the same
+ * rank order with the raw tunnel_endpoint as the leaf value, so that for
+ * every address the leaf comes from the entry the identity comes from.  The
+ * leaves do not tell "no match" from "tunnel 0" (both decode to 0): a kernel
+ * gates on the identity lookup.  Equal tunnel values share one `vals` word,
+ * so that a cluster's few node addresses fit the lpm16c leaf dictionary.
+ * Kept beside the snapshot, not in it (kernels without a tunnel output keep
+ * their kernarg layout); t4.d16 == NULL: not compiled (flag off). */
+typedef struct ipc_tun {
+	lpm16c t4;
+	v6_lpm t6;
+} ipc_tun;
+
 /* ---- conntrack map cilium_ct4_global ----
  * Open addressing with linear probing over nslots = 2^k >= 2 * max slots.
  * keys[slot] (16 B, one gather per probe) = the 14-byte struct ipv4_ct_tuple

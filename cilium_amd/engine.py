@@ -419,9 +419,38 @@ class Engine:
         return s.value
 
     # -------------------------------------------------------------- batches
-    def classify_v4(self, t: dict, out: dict | None = None, stage: bool = True, stream=None):
+    PATH_PLAIN, PATH_LB, PATH_CASCADE = 0, 1, 2
+
+    def _classify_tun(self, v6: bool, path: int, t: dict, out, stage, stream):
+        """cgpu_classify_v4_tun / _v6_tun: the stateless call `path` names
+        with out["tunnel"] (int32 holding the raw u32) as one more output:
+        the tunnel_endpoint of the ipcache entry an egress tuple's identity
+        came from, 0 elsewhere (include/cgpu.h).  Needs
+        Engine(ipcache_tunnel=1)."""
+        import torch
+        n = t["flags"].numel()
+        dev = t["flags"].device
+        if out is None:
+            out = {"verdict": torch.empty(n, dtype=torch.int32, device=dev),
+                   "identity": torch.empty(n, dtype=torch.int32, device=dev),
+                   "stage": torch.empty(n, dtype=torch.uint8, device=dev) if stage else None}
+        if out.get("tunnel") is None:
+            out["tunnel"] = torch.empty(n, dtype=torch.int32, device=dev)
+        tv = (TuplesV6 if v6 else TuplesV4)(*[t[k].data_ptr() for k in
+                                              ("saddr", "daddr", "dport", "proto", "flags", "len", "ep")])
+        fn = "cgpu_classify_v6_tun" if v6 else "cgpu_classify_v4_tun"
+        check(getattr(self.L, fn)(self.h, C.byref(tv), _ptr(t.get("sport")), _ptr(t.get("hash")), path, n,
+                                  _ptr(out["verdict"]), _ptr(out["identity"]), _ptr(out.get("stage")),
+                                  _ptr(out["tunnel"]), _stream(stream)), fn)
+        return out
+
+    def classify_v4(self, t: dict, out: dict | None = None, stage: bool = True, stream=None,
+                    tunnel: bool = False):
         """t: dict of CUDA tensors saddr/daddr (int32 view of network-order
-        u32), dport (int16), proto/flags (uint8), len (int32), ep (int16)."""
+        u32), dport (int16), proto/flags (uint8), len (int32), ep (int16).
+        tunnel=True: out["tunnel"] too (_classify_tun)."""
+        if tunnel:
+            return self._classify_tun(False, self.PATH_PLAIN, t, out, stage, stream)
         import torch
         n = t["saddr"].numel()
         dev = t["saddr"].device
@@ -496,12 +525,37 @@ class Engine:
             (stream or torch.cuda.current_stream()).synchronize()
         return out
 
+    def _ct_tun(self, v6: bool, t: dict, now: int, out, stage, stream):
+        """cgpu_classify_v4_ct_tun / _v6_ct_tun: the plain stateful call with
+        out["tunnel"] (int32 holding the raw u32), the forward tuple's tunnel
+        endpoint (include/cgpu.h).  Needs Engine(ipcache_tunnel=1)."""
+        import torch
+        n = t["flags"].numel()
+        dev = t["flags"].device
+        if out is None:
+            out = {"verdict": torch.empty(n, dtype=torch.int32, device=dev),
+                   "ct_ret": torch.empty(n, dtype=torch.uint8, device=dev),
+                   "identity": torch.empty(n, dtype=torch.int32, device=dev),
+                   "stage": torch.empty(n, dtype=torch.uint8, device=dev) if stage else None}
+        if out.get("tunnel") is None:
+            out["tunnel"] = torch.empty(n, dtype=torch.int32, device=dev)
+        tv = (TuplesV6Ct if v6 else TuplesV4Ct)(*[t[k].data_ptr() for k in (
+            "saddr", "daddr", "sport", "dport", "proto", "l4b", "flags", "len", "ep")])
+        fn = "cgpu_classify_v6_ct_tun" if v6 else "cgpu_classify_v4_ct_tun"
+        check(getattr(self.L, fn)(self.h, C.byref(tv), n, now, _ptr(out["verdict"]), _ptr(out["ct_ret"]),
+                                  _ptr(out["identity"]), _ptr(out.get("stage")), _ptr(out["tunnel"]),
+                                  _stream(stream)), fn)
+        return out
+
     def classify_v4_ct(self, t: dict, now: int, out: dict | None = None, stage: bool = True,
-                       stream=None):
+                       stream=None, tunnel: bool = False):
         """Stateful classification (cgpu_classify_v4_ct): t holds CUDA tensors
         saddr/daddr (int32), sport/dport (int16, network order), proto/flags
         (uint8), l4b (int16: TCP header bytes 12-13 / ICMP type), len (int32),
-        ep (int16); now = bpf_ktime_get_sec() of the batch."""
+        ep (int16); now = bpf_ktime_get_sec() of the batch.
+        tunnel=True: out["tunnel"] too (_ct_tun)."""
+        if tunnel:
+            return self._ct_tun(False, t, now, out, stage, stream)
         import torch
         n = t["saddr"].numel()
         dev = t["saddr"].device
@@ -543,9 +597,11 @@ class Engine:
         return out
 
     def classify_v6_ct(self, t: dict, now: int, out: dict | None = None, stage: bool = True,
-                       stream=None):
+                       stream=None, tunnel: bool = False):
         """cgpu_classify_v6_ct: as classify_v4_ct with saddr / daddr (n, 16)
         uint8 tensors (16-byte aligned rows)."""
+        if tunnel:
+            return self._ct_tun(True, t, now, out, stage, stream)
         import torch
         n = t["saddr"].shape[0]
         dev = t["saddr"].device
@@ -586,11 +642,15 @@ class Engine:
         return out
 
     def classify_v4_lb(self, t: dict, out: dict | None = None, stage: bool = True, stream=None,
-                       xdp: bool = False):
+                       xdp: bool = False, tunnel: bool = False):
         """classify_v4 with the egress service step first (BASELINE config 5).
         t additionally holds "hash" (int32 view of skb->hash) or "sport".
         xdp=True: cgpu_classify_v4_cascade, the netdev's XDP prefilter before
-        every ingress tuple too (the full config-5 cascade)."""
+        every ingress tuple too (the full config-5 cascade).
+        tunnel=True: out["tunnel"] too (_classify_tun)."""
+        if tunnel:
+            return self._classify_tun(False, self.PATH_CASCADE if xdp else self.PATH_LB, t, out, stage,
+                                      stream)
         import torch
         n = t["saddr"].numel()
         dev = t["saddr"].device
@@ -606,11 +666,12 @@ class Engine:
                                   _stream(stream)), fn)
         return out
 
-    def classify_v4_cascade(self, t: dict, out: dict | None = None, stage: bool = True, stream=None):
+    def classify_v4_cascade(self, t: dict, out: dict | None = None, stage: bool = True, stream=None,
+                            tunnel: bool = False):
         """BASELINE config 5 whole (cgpu_classify_v4_cascade): XDP prefilter
         -> ipcache -> policy for ingress tuples, service step -> ipcache ->
         policy for egress ones."""
-        return self.classify_v4_lb(t, out=out, stage=stage, stream=stream, xdp=True)
+        return self.classify_v4_lb(t, out=out, stage=stage, stream=stream, xdp=True, tunnel=tunnel)
 
     def lb4_select(self, t: dict, mode: int, out: dict | None = None, stream=None):
         """Service translation alone: t holds saddr/daddr (int32 views),
@@ -633,9 +694,12 @@ class Engine:
               "cgpu_lb4_select")
         return out
 
-    def classify_v6(self, t: dict, out: dict | None = None, stage: bool = True, stream=None):
+    def classify_v6(self, t: dict, out: dict | None = None, stage: bool = True, stream=None,
+                    tunnel: bool = False):
         """t: saddr/daddr uint8 CUDA tensors of shape (n, 16) (16-byte
         aligned), the other columns as classify_v4."""
+        if tunnel:
+            return self._classify_tun(True, self.PATH_PLAIN, t, out, stage, stream)
         import torch
         n = t["flags"].numel()
         dev = t["flags"].device
@@ -650,9 +714,12 @@ class Engine:
                                       _stream(stream)), "cgpu_classify_v6")
         return out
 
-    def classify_v6_lb(self, t: dict, out: dict | None = None, stage: bool = True, stream=None):
+    def classify_v6_lb(self, t: dict, out: dict | None = None, stage: bool = True, stream=None,
+                       tunnel: bool = False):
         """classify_v6 with the egress service step of ipv6_l3_from_lxc first;
         t additionally holds "hash" (int32 view of skb->hash) or "sport"."""
+        if tunnel:
+            return self._classify_tun(True, self.PATH_LB, t, out, stage, stream)
         import torch
         n = t["flags"].numel()
         dev = t["flags"].device
@@ -666,6 +733,33 @@ class Engine:
                                          _ptr(t.get("hash")), n, _ptr(out["verdict"]),
                                          _ptr(out["identity"]), _ptr(out.get("stage")),
                                          _stream(stream)), "cgpu_classify_v6_lb")
+        return out
+
+    def ipcache_lookup_batch(self, addr, tunnel: bool | None = None, stream=None):
+        """cgpu_ipcache_lookup_v4 / _v6: ipcache_lookup4 / 6 (eps.h:56-80) of a
+        batch of addresses on the device.  addr: a uint32 / int32 CUDA tensor
+        (network-order IPv4) or an (n, 16) uint8 one (IPv6, any alignment).
+        Returns {"found" (uint8; a tombstone is found), "sec_label",
+        "tunnel"} -- int32 tensors holding the raw u32 words; "tunnel" is
+        None without Engine(ipcache_tunnel=1) (tunnel=True asks for it
+        regardless: -EINVAL there)."""
+        import torch
+        v6 = addr.dtype == torch.uint8
+        if v6:
+            assert addr.dim() == 2 and addr.shape[1] == 16 and addr.stride(1) == 1 and \
+                (addr.shape[0] < 2 or addr.stride(0) == 16), "IPv6 addresses: dense (n, 16) uint8"
+        else:
+            assert addr.dtype in (torch.int32, torch.uint32) and addr.is_contiguous(), \
+                "IPv4 addresses: a contiguous 32-bit tensor"
+        n = addr.shape[0]
+        if tunnel is None:
+            tunnel = bool(self.cfg.ipcache_tunnel)
+        out = {"found": torch.empty(n, dtype=torch.uint8, device=addr.device),
+               "sec_label": torch.empty(n, dtype=torch.int32, device=addr.device),
+               "tunnel": torch.empty(n, dtype=torch.int32, device=addr.device) if tunnel else None}
+        fn = "cgpu_ipcache_lookup_v6" if v6 else "cgpu_ipcache_lookup_v4"
+        check(getattr(self.L, fn)(self.h, _ptr(addr), n, _ptr(out["found"]), _ptr(out["sec_label"]),
+                                  _ptr(out["tunnel"]), _stream(stream)), fn)
         return out
 
     def prefilter_v4(self, saddr, daddr, flags, out=None, stream=None):

@@ -179,7 +179,14 @@ typedef struct cgpu_config {
 	 * keep failing the create (DROP_NO_SERVICE / DROP_CT_CREATE_FAILED).
 	 * 0 (default): the non-LRU build, CT_MAP_SIZE enforced as -E2BIG. */
 	uint32_t ct_lru;
-	uint32_t reserved[1];
+	/* 1: cgpu_commit also compiles the second word of every ipcache value,
+	 * struct remote_endpoint_info.tunnel_endpoint (bpf/lib/common.h:175-178),
+	 * into device tables, and the calls with a `tunnel` output may be given
+	 * one.  0 (default): the device holds identities only, exactly the tables
+	 * and bytes of a build without this field, and every such call given a
+	 * non-NULL tunnel pointer returns -EINVAL.  (Was reserved[0]; the struct
+	 * size and CGPU_ABI_VERSION stay.) */
+	uint32_t ipcache_tunnel;
 } cgpu_config;
 
 #define CGPU_SCHED_PER_LANE 1u   /* classify: one tuple per lane (k_classify) instead of x4 */
@@ -222,6 +229,20 @@ size_t cgpu_ipcache_count(cgpu_ctx *ctx);
  * OnIPIdentityCacheChange writes in one call */
 int cgpu_ipcache_update_batch(cgpu_ctx *ctx, const cgpu_ipcache_key *keys,
 			      const cgpu_remote_endpoint_info *vals, size_t n, uint64_t flags);
+/* ipcache_lookup4 / ipcache_lookup6 (bpf/lib/eps.h:56-80) over a batch of
+ * addresses on the device, against the committed snapshot (device pointers;
+ * addr: network-order u32, addr16: 16 bytes per address, any alignment).
+ * found[i] = 1 for any match, a tombstone (sec_label 0) included; sec_label[i]
+ * and tunnel[i] are the matched entry's raw words {sec_label, tunnel_endpoint}
+ * (bpf/lib/common.h:175-178), 0 where nothing matched.  The tunnel is the
+ * word the reference reads as info->tunnel_endpoint on every forwarded egress
+ * packet (bpf_lxc.c:488-491 IPv4, :177-180 IPv6).  found, sec_label and tunnel
+ * may each be NULL; tunnel must be NULL unless cgpu_config.ipcache_tunnel is
+ * set (-EINVAL).  -ENODEV on a host-only context. */
+int cgpu_ipcache_lookup_v4(cgpu_ctx *ctx, const uint32_t *addr, size_t n, uint8_t *found,
+			   uint32_t *sec_label, uint32_t *tunnel, void *stream);
+int cgpu_ipcache_lookup_v6(cgpu_ctx *ctx, const uint8_t *addr16, size_t n, uint8_t *found,
+			   uint32_t *sec_label, uint32_t *tunnel, void *stream);
 
 /* ------------------------------------------------------------------ */
 /* policy maps: pkg/maps/policymap (AllowKey/DeleteKey/DumpToSlice/     */
@@ -560,6 +581,39 @@ int cgpu_classify_v6_lb(cgpu_ctx *ctx, const cgpu_tuples_v6 *t, const uint16_t *
 			uint8_t *stage, void *stream);
 
 /*
+ * The stateless paths above with the tunnel endpoint of every tuple as one
+ * more output (cgpu_config.ipcache_tunnel).  path selects the call this is:
+ * CGPU_PATH_PLAIN cgpu_classify_v4 / _v6 (sport and hash ignored),
+ * CGPU_PATH_LB cgpu_classify_v4_lb / _v6_lb, CGPU_PATH_CASCADE
+ * cgpu_classify_v4_cascade (IPv4 only); verdicts, identities, stages,
+ * counters and metrics are that call's.
+ *   tunnel[i] = the reference's local tunnel_endpoint behind bpf_lxc.c:488-491
+ *   (IPv4) / :177-180 (IPv6), which :595-598 / :291-294 hand to
+ *   encap_and_redirect_with_nodeid: the tunnel_endpoint of the ipcache entry
+ *   the identity came from (struct remote_endpoint_info, bpf/lib/common.h:
+ *   175-178; ipcache_lookup4 / 6, bpf/lib/eps.h:56-80) when the tuple is
+ *   egress, reached the lookup and matched an entry with sec_label != 0;
+ *   0 otherwise: ingress tuples, no match, a label-0 (tombstone) match, and
+ *   tuples that end before the lookup (stage 4 protocol gate, stage 6
+ *   service drop, stage 8 XDP drop).  With the service step the address
+ *   looked up is the one the identity is looked up on, the daddr after
+ *   translation.  The value does not depend on the policy verdict: the
+ *   consumer decides about encapsulation.  Every element is written.
+ * tunnel == NULL: exactly the call `path` names.  -ENODEV on a host-only
+ * context; -EINVAL for a bad path, or a non-NULL tunnel on a context without
+ * cgpu_config.ipcache_tunnel.
+ */
+#define CGPU_PATH_PLAIN 0
+#define CGPU_PATH_LB 1
+#define CGPU_PATH_CASCADE 2 /* v4 only */
+int cgpu_classify_v4_tun(cgpu_ctx *ctx, const cgpu_tuples_v4 *t, const uint16_t *sport,
+			 const uint32_t *hash, int path, size_t n, int32_t *verdict, uint32_t *identity,
+			 uint8_t *stage, uint32_t *tunnel, void *stream);
+int cgpu_classify_v6_tun(cgpu_ctx *ctx, const cgpu_tuples_v6 *t, const uint16_t *sport,
+			 const uint32_t *hash, int path, size_t n, int32_t *verdict, uint32_t *identity,
+			 uint8_t *stage, uint32_t *tunnel, void *stream);
+
+/*
  * The HOST-resident forms of the service, cascade and IPv6 paths: the same
  * arguments, results, counters and metrics as the device call of the same
  * name without _host, with every column and output a host pointer, streamed
@@ -824,6 +878,19 @@ typedef struct cgpu_tuples_v4_ct {
 int cgpu_classify_v4_ct(cgpu_ctx *ctx, const cgpu_tuples_v4_ct *t, size_t n, uint32_t now,
 			int32_t *verdict, uint8_t *ct_ret, uint32_t *identity, uint8_t *stage,
 			void *stream);
+/* cgpu_classify_v4_ct with the tunnel endpoint of every packet's forward tuple
+ * as one more output (cgpu_config.ipcache_tunnel; the rule of
+ * cgpu_classify_v4_tun, bpf_lxc.c:488-491): the ipcache entry's
+ * tunnel_endpoint (bpf/lib/common.h:175-178) for an egress packet whose
+ * ct_lookup4 succeeded (ct_ret != CGPU_CT_NONE) and whose daddr matched an
+ * entry with sec_label != 0, whatever ct_ret and the verdict are (a CT_REPLY
+ * packet skips the policy, not the lookup); 0 otherwise.  Results, counters
+ * and the conntrack map are cgpu_classify_v4_ct's.  tunnel == NULL: that
+ * call.  -ENODEV on a host-only context, -EINVAL for a non-NULL tunnel
+ * without the flag. */
+int cgpu_classify_v4_ct_tun(cgpu_ctx *ctx, const cgpu_tuples_v4_ct *t, size_t n, uint32_t now,
+			    int32_t *verdict, uint8_t *ct_ret, uint32_t *identity, uint8_t *stage,
+			    uint32_t *tunnel, void *stream);
 
 /* outputs of cgpu_classify_v4_ctlb (device pointers; stage, daddr, dport
  * may be NULL) */
@@ -923,6 +990,10 @@ typedef struct cgpu_tuples_v6_ct {
 int cgpu_classify_v6_ct(cgpu_ctx *ctx, const cgpu_tuples_v6_ct *t, size_t n, uint32_t now,
 			int32_t *verdict, uint8_t *ct_ret, uint32_t *identity, uint8_t *stage,
 			void *stream);
+/* as cgpu_classify_v4_ct_tun over IPv6 (bpf_lxc.c:177-180) */
+int cgpu_classify_v6_ct_tun(cgpu_ctx *ctx, const cgpu_tuples_v6_ct *t, size_t n, uint32_t now,
+			    int32_t *verdict, uint8_t *ct_ret, uint32_t *identity, uint8_t *stage,
+			    uint32_t *tunnel, void *stream);
 
 /* cgpu_classify_v6_ctlb's outputs: as cgpu_ctlb_out with the frame's daddr
  * 16 bytes per packet (16-byte aligned) */
