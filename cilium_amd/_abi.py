@@ -70,6 +70,14 @@ class CtlbOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("verdict", "ct_ret", "identity", "stage", "daddr", "dport")]
 
 
+class Rnat4Out(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("saddr", "daddr", "sport", "applied")]
+
+
+class Rnat6Out(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("saddr", "sport", "applied")]
+
+
 class Frames(C.Structure):
     _fields_ = [("data", C.c_void_p), ("len", C.c_void_p), ("flags", C.c_void_p),
                 ("ep", C.c_void_p), ("stride", C.c_uint32), ("reserved", C.c_uint32)]
@@ -81,6 +89,7 @@ class FrameTuples(C.Structure):
 
 
 vp, sz, u32, u64, i32 = C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint64, C.c_int
+u16 = C.c_uint16
 
 # name -> (restype, argtypes)
 PROTOS = {
@@ -129,6 +138,16 @@ PROTOS = {
     "cgpu_lb6_lookup": (i32, [vp, vp, vp]),
     "cgpu_lb6_get_next_key": (i32, [vp, vp, vp]),
     "cgpu_lb6_count": (sz, [vp]),
+    "cgpu_revnat4_update": (i32, [vp, u16, vp, u64]),
+    "cgpu_revnat4_delete": (i32, [vp, u16]),
+    "cgpu_revnat4_lookup": (i32, [vp, u16, vp]),
+    "cgpu_revnat4_get_next_key": (i32, [vp, C.POINTER(u16), C.POINTER(u16)]),
+    "cgpu_revnat4_count": (sz, [vp]),
+    "cgpu_revnat6_update": (i32, [vp, u16, vp, u64]),
+    "cgpu_revnat6_delete": (i32, [vp, u16]),
+    "cgpu_revnat6_lookup": (i32, [vp, u16, vp]),
+    "cgpu_revnat6_get_next_key": (i32, [vp, C.POINTER(u16), C.POINTER(u16)]),
+    "cgpu_revnat6_count": (sz, [vp]),
     "cgpu_flow_hash6": (u32, [vp, vp, C.c_uint16, C.c_uint16, C.c_uint8]),
     "cgpu_flow_hash": (u32, [u32, u32, C.c_uint16, C.c_uint16, C.c_uint8]),
     "cgpu_commit": (i32, [vp, C.POINTER(u64)]),
@@ -182,6 +201,14 @@ PROTOS = {
     "cgpu_ct6_flush": (i32, [vp]),
     "cgpu_classify_v6_ctlb": (i32, [vp, C.POINTER(TuplesV6Ct), vp, sz, u32, C.POINTER(CtlbOut), vp]),
     "cgpu_classify_v6_ct": (i32, [vp, C.POINTER(TuplesV6Ct), sz, u32, vp, vp, vp, vp, vp]),
+    "cgpu_classify_v4_ct_rnat": (i32, [vp, C.POINTER(TuplesV4Ct), sz, u32, vp, vp, vp, vp,
+                                       C.POINTER(Rnat4Out), vp]),
+    "cgpu_classify_v4_ctlb_rnat": (i32, [vp, C.POINTER(TuplesV4Ct), vp, sz, u32, C.POINTER(CtlbOut),
+                                         C.POINTER(Rnat4Out), vp]),
+    "cgpu_classify_v6_ct_rnat": (i32, [vp, C.POINTER(TuplesV6Ct), sz, u32, vp, vp, vp, vp,
+                                       C.POINTER(Rnat6Out), vp]),
+    "cgpu_classify_v6_ctlb_rnat": (i32, [vp, C.POINTER(TuplesV6Ct), vp, sz, u32, C.POINTER(CtlbOut),
+                                         C.POINTER(Rnat6Out), vp]),
     "cgpu_l3_compile": (i32, [vp, vp, vp, vp, u32, vp]),
     "cgpu_mapstate_sync": (i32, [vp, vp, vp, vp, vp, vp]),
     "cgpu_counter_delta_bytes": (sz, [vp]),

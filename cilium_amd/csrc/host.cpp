@@ -46,6 +46,8 @@ static_assert(sizeof(pol_slot) == 16, "policy slot");
 static_assert(sizeof(set16_slot) == 32, "set16 slot");
 static_assert(sizeof(cgpu_lb4_key) == 8, "lb4_key layout");
 static_assert(sizeof(cgpu_lb4_service) == 12, "lb4_service layout");
+static_assert(sizeof(cgpu_lb4_reverse_nat) == 6, "lb4_reverse_nat layout");
+static_assert(sizeof(cgpu_lb6_reverse_nat) == 18, "lb6_reverse_nat layout");
 static_assert(sizeof(cgpu_lb6_key) == 20, "lb6_key layout");
 static_assert(sizeof(cgpu_lb6_service) == 24, "lb6_service layout");
 
@@ -1961,6 +1963,13 @@ struct cgpu_ctx {
 	 * a frontend's entries are adjacent */
 	std::map<uint64_t, cgpu_lb4_service> lb;
 	std::map<Lb6K, cgpu_lb6_service> lb6;
+	/* cilium_lb4_reverse_nat / cilium_lb6_reverse_nat, keyed by the raw index
+	 * word; their dense device tables (NULL while a map is empty) are rebuilt
+	 * by a commit after a change and read only on the conntrack stream */
+	std::map<uint16_t, cgpu_lb4_reverse_nat> rn4;
+	std::map<uint16_t, cgpu_lb6_reverse_nat> rn6;
+	bool rn4_dirty = false, rn6_dirty = false;
+	void *d_rn4 = nullptr, *d_rn6 = nullptr;
 	/* per-endpoint lxc_config.h identity (cgpu_lxc_update) */
 	std::map<uint32_t, cgpu_lxc_info> lxcinfo;
 	int64_t pf_revision = 1; /* PreFilter revision (pkg/policy/prefilter.go:283) */
@@ -2318,6 +2327,8 @@ CGPU_EXPORT void cgpu_ctx_destroy(cgpu_ctx *c)
 		}
 		(void)hipFree(c->d_ct_scratch);
 		(void)hipFree(c->d_ct_pk);
+		(void)hipFree(c->d_rn4);
+		(void)hipFree(c->d_rn6);
 		host_stage_free(c);
 		(void)hipEventDestroy(c->ct_done);
 		(void)hipStreamDestroy(c->ct_stream);
@@ -3124,6 +3135,161 @@ CGPU_EXPORT size_t cgpu_lb4_count(cgpu_ctx *c)
 		return 0;
 	std::lock_guard<std::mutex> g(c->mu);
 	return c->lb.size();
+}
+
+/* ---- cilium_lb4_reverse_nat / cilium_lb6_reverse_nat (lb.h:54-68; the agent:
+ * pkg/maps/lbmap/lbmap.go:229-260) ---- */
+template <class V>
+static int rn_put(cgpu_ctx *c, std::map<uint16_t, V> &m, bool &dirty, uint16_t index, const V *val,
+		  uint64_t flags, const char *what)
+{
+	if (!c || !val)
+		return fail(-EINVAL, "null argument");
+	if (int r = check_flags(flags))
+		return r;
+	std::lock_guard<std::mutex> g(c->mu);
+	auto it = m.find(index);
+	if (it == m.end()) {
+		if (flags == CGPU_EXIST)
+			return fail(-ENOENT, "%s index not present", what);
+		if (m.size() >= c->cfg.lb_max_entries)
+			return fail(-E2BIG, "%s map full (%u)", what, c->cfg.lb_max_entries);
+		m.emplace(index, *val);
+	} else {
+		if (flags == CGPU_NOEXIST)
+			return fail(-EEXIST, "%s index exists", what);
+		it->second = *val;
+	}
+	dirty = true;
+	return 0;
+}
+
+template <class V> static int rn_del(cgpu_ctx *c, std::map<uint16_t, V> &m, bool &dirty, uint16_t index)
+{
+	if (!c)
+		return fail(-EINVAL, "null argument");
+	std::lock_guard<std::mutex> g(c->mu);
+	if (!m.erase(index))
+		return -ENOENT;
+	dirty = true;
+	return 0;
+}
+
+template <class V> static int rn_get(cgpu_ctx *c, std::map<uint16_t, V> &m, uint16_t index, V *out)
+{
+	if (!c || !out)
+		return fail(-EINVAL, "null argument");
+	std::lock_guard<std::mutex> g(c->mu);
+	auto it = m.find(index);
+	if (it == m.end())
+		return -ENOENT;
+	*out = it->second;
+	return 0;
+}
+
+template <class V>
+static int rn_next(cgpu_ctx *c, std::map<uint16_t, V> &m, const uint16_t *index, uint16_t *next)
+{
+	if (!c || !next)
+		return fail(-EINVAL, "null argument");
+	std::lock_guard<std::mutex> g(c->mu);
+	auto it = index ? m.upper_bound(*index) : m.begin();
+	if (it == m.end())
+		return -ENOENT;
+	*next = it->first;
+	return 0;
+}
+
+CGPU_EXPORT int cgpu_revnat4_update(cgpu_ctx *c, uint16_t index, const cgpu_lb4_reverse_nat *val, uint64_t flags)
+{
+	return c ? rn_put(c, c->rn4, c->rn4_dirty, index, val, flags, "lb4 reverse NAT") : fail(-EINVAL, "null argument");
+}
+CGPU_EXPORT int cgpu_revnat4_delete(cgpu_ctx *c, uint16_t index)
+{
+	return c ? rn_del(c, c->rn4, c->rn4_dirty, index) : fail(-EINVAL, "null argument");
+}
+CGPU_EXPORT int cgpu_revnat4_lookup(cgpu_ctx *c, uint16_t index, cgpu_lb4_reverse_nat *val_out)
+{
+	return c ? rn_get(c, c->rn4, index, val_out) : fail(-EINVAL, "null argument");
+}
+CGPU_EXPORT int cgpu_revnat4_get_next_key(cgpu_ctx *c, const uint16_t *index, uint16_t *next_out)
+{
+	return c ? rn_next(c, c->rn4, index, next_out) : fail(-EINVAL, "null argument");
+}
+CGPU_EXPORT size_t cgpu_revnat4_count(cgpu_ctx *c)
+{
+	if (!c)
+		return 0;
+	std::lock_guard<std::mutex> g(c->mu);
+	return c->rn4.size();
+}
+CGPU_EXPORT int cgpu_revnat6_update(cgpu_ctx *c, uint16_t index, const cgpu_lb6_reverse_nat *val, uint64_t flags)
+{
+	return c ? rn_put(c, c->rn6, c->rn6_dirty, index, val, flags, "lb6 reverse NAT") : fail(-EINVAL, "null argument");
+}
+CGPU_EXPORT int cgpu_revnat6_delete(cgpu_ctx *c, uint16_t index)
+{
+	return c ? rn_del(c, c->rn6, c->rn6_dirty, index) : fail(-EINVAL, "null argument");
+}
+CGPU_EXPORT int cgpu_revnat6_lookup(cgpu_ctx *c, uint16_t index, cgpu_lb6_reverse_nat *val_out)
+{
+	return c ? rn_get(c, c->rn6, index, val_out) : fail(-EINVAL, "null argument");
+}
+CGPU_EXPORT int cgpu_revnat6_get_next_key(cgpu_ctx *c, const uint16_t *index, uint16_t *next_out)
+{
+	return c ? rn_next(c, c->rn6, index, next_out) : fail(-EINVAL, "null argument");
+}
+CGPU_EXPORT size_t cgpu_revnat6_count(cgpu_ctx *c)
+{
+	if (!c)
+		return 0;
+	std::lock_guard<std::mutex> g(c->mu);
+	return c->rn6.size();
+}
+
+/* The reverse-NAT maps' device form (a commit, after a change): dense by the
+ * raw index, IPv4 65,536 x 8 B {address, port | 1 << 16}, IPv6 65,536 x 32 B
+ * {address}, {port | 1 << 16, 0, 0, 0}; an empty map has no table.  Only the
+ * conntrack stream reads them, and it is drained before a table changes. */
+static int rn_upload(cgpu_ctx *c)
+{
+	std::lock_guard<std::mutex> g(c->mu);
+	if (!c->rn4_dirty && !c->rn6_dirty)
+		return 0;
+	HIP_OR_EIO(hipStreamSynchronize(c->ct_stream));
+	if (c->rn4_dirty) {
+		if (c->rn4.empty()) {
+			(void)hipFree(c->d_rn4);
+			c->d_rn4 = nullptr;
+		} else {
+			std::vector<uint32_t> t(2u * 65536u, 0u);
+			for (auto &kv : c->rn4) {
+				t[2u * kv.first] = kv.second.address;
+				t[2u * kv.first + 1u] = (uint32_t)kv.second.port | 1u << 16;
+			}
+			if (!c->d_rn4)
+				HIP_OR_EIO(hipMalloc(&c->d_rn4, t.size() * 4u));
+			HIP_OR_EIO(hipMemcpy(c->d_rn4, t.data(), t.size() * 4u, hipMemcpyHostToDevice));
+		}
+		c->rn4_dirty = false;
+	}
+	if (c->rn6_dirty) {
+		if (c->rn6.empty()) {
+			(void)hipFree(c->d_rn6);
+			c->d_rn6 = nullptr;
+		} else {
+			std::vector<uint32_t> t(8u * 65536u, 0u);
+			for (auto &kv : c->rn6) {
+				memcpy(&t[8u * kv.first], kv.second.address, 16);
+				t[8u * kv.first + 4u] = (uint32_t)kv.second.port | 1u << 16;
+			}
+			if (!c->d_rn6)
+				HIP_OR_EIO(hipMalloc(&c->d_rn6, t.size() * 4u));
+			HIP_OR_EIO(hipMemcpy(c->d_rn6, t.data(), t.size() * 4u, hipMemcpyHostToDevice));
+		}
+		c->rn6_dirty = false;
+	}
+	return 0;
 }
 
 static int lb6_put(cgpu_ctx *c, const cgpu_lb6_key *key, const cgpu_lb6_service *val, uint64_t flags)
@@ -4010,6 +4176,8 @@ static int commit_locked(cgpu_ctx *c, uint64_t *epoch_out)
 		capture(c, in, c->b);
 	}
 	HIP_OR_EIO(hipSetDevice(c->device));
+	if (int r = rn_upload(c))
+		return r;
 	std::shared_ptr<Epoch> prev;
 	{
 		std::lock_guard<std::mutex> g(c->pub_mu);
@@ -6225,10 +6393,10 @@ CGPU_EXPORT int cgpu_ct6_flush(cgpu_ctx *c)
 /* scratch of one cgpu_classify_v{4,6}_ct launch over n packets */
 struct CtScratch {
 	size_t rec, gkey, gkey_sorted, idx, idx_sorted, heads, n_heads, heads_pos, head,
-		temp, temp_bytes, svc_out, ctl, flags2, pcls, total;
+		temp, temp_bytes, svc_out, ctl, flags2, pcls, rn, total;
 };
 
-static CtScratch ct_scratch_layout(uint64_t n, size_t rec_bytes, bool svc, bool v6)
+static CtScratch ct_scratch_layout(uint64_t n, size_t rec_bytes, bool svc, bool v6, bool rn = false)
 {
 	CtScratch L{};
 	auto take = [&](size_t bytes) {
@@ -6253,12 +6421,14 @@ static CtScratch ct_scratch_layout(uint64_t n, size_t rec_bytes, bool svc, bool 
 		L.ctl = take(16);
 		L.pcls = take(n);
 	}
+	if (rn) /* after everything else: the other offsets are those of a call without it */
+		L.rn = take(n * 4);
 	return L;
 }
 
 /* one stateful batch on map m: columns already validated by the caller */
 static int ct_classify(cgpu_ctx *c, const cgpu_snapshot &s, uint64_t *delta, CtMap &m, ct_launch a,
-		       void *stream, bool svc = false)
+		       void *stream, bool svc = false, bool rnat = false)
 {
 	/* One conntrack map, one scratch: every batch runs on the context's
 	 * conntrack stream, after the caller's stream reaches this call (its
@@ -6284,7 +6454,7 @@ static int ct_classify(cgpu_ctx *c, const cgpu_snapshot &s, uint64_t *delta, CtM
 	}
 	if (int r = ct_push(m))
 		return r;
-	const CtScratch L = ct_scratch_layout(a.n, m.v6 ? 64 : svc ? 48 : 32, svc, m.v6);
+	const CtScratch L = ct_scratch_layout(a.n, m.v6 ? 64 : svc ? 48 : 32, svc, m.v6, rnat);
 	if (L.total > c->ct_scratch_cap) {
 		HIP_OR_EIO(hipStreamSynchronize(cs));
 		(void)hipFree(c->d_ct_scratch);
@@ -6327,6 +6497,13 @@ static int ct_classify(cgpu_ctx *c, const cgpu_snapshot &s, uint64_t *delta, CtM
 	a.flags2 = b + L.flags2;
 	a.pk = c->d_ct_pk;
 	a.dflt = 1u; /* group-default results (kernels.hip CT_DFLT; the launchers clear it where a prep stores every result) */
+	if (rnat) {
+		/* the walkers store only nonzero indices */
+		a.rn = reinterpret_cast<uint32_t *>(b + L.rn);
+		HIP_OR_EIO(hipMemsetAsync(a.rn, 0, a.n * 4u, cs));
+		a.rn_t4 = c->d_rn4;
+		a.rn_t6 = c->d_rn6;
+	}
 	hipError_t le;
 	if (svc) {
 		a.svc_out = reinterpret_cast<uint4 *>(b + L.svc_out);
@@ -6349,8 +6526,32 @@ static int ct_classify(cgpu_ctx *c, const cgpu_snapshot &s, uint64_t *delta, CtM
 }
 
 /* cgpu_classify_v4_ct; tunnel: NULL, or cgpu_classify_v4_ct_tun's output */
+/* the _rnat entry points' outputs into a launch (rn == NULL: none) */
+static void rnat4_into(ct_launch &a, const cgpu_rnat4_out *rn)
+{
+	if (!rn)
+		return;
+	a.rn_saddr = rn->saddr;
+	a.rn_daddr = rn->daddr;
+	a.rn_sport = rn->sport;
+	a.rn_applied = rn->applied;
+}
+
+static int rnat6_into(ct_launch &a, const cgpu_rnat6_out *rn)
+{
+	if (!rn)
+		return 0;
+	if ((uintptr_t)rn->saddr & 15)
+		return fail(-EINVAL, "IPv6 address columns must be 16-byte aligned");
+	a.rn_saddr = rn->saddr;
+	a.rn_sport = rn->sport;
+	a.rn_applied = rn->applied;
+	return 0;
+}
+
 static int classify_v4_ct(cgpu_ctx *c, const cgpu_tuples_v4_ct *t, size_t n, uint32_t now, int32_t *verdict,
-			  uint8_t *ct_ret, uint32_t *identity, uint8_t *stage, uint32_t *tunnel, void *stream)
+			  uint8_t *ct_ret, uint32_t *identity, uint8_t *stage, uint32_t *tunnel, void *stream,
+			  const cgpu_rnat4_out *rn = nullptr)
 {
 	Pinned P;
 	if (int r = pin(c, stream, P))
@@ -6380,7 +6581,15 @@ static int classify_v4_ct(cgpu_ctx *c, const cgpu_tuples_v4_ct *t, size_t n, uin
 	a.now = now;
 	a.tunnel = tunnel;
 	a.tun = &P.tun();
-	return ct_classify(c, P.snap(), P.delta, c->ct4, a, stream);
+	rnat4_into(a, rn);
+	return ct_classify(c, P.snap(), P.delta, c->ct4, a, stream, false, rn != nullptr);
+}
+
+CGPU_EXPORT int cgpu_classify_v4_ct_rnat(cgpu_ctx *c, const cgpu_tuples_v4_ct *t, size_t n, uint32_t now,
+					 int32_t *verdict, uint8_t *ct_ret, uint32_t *identity,
+					 uint8_t *stage, const cgpu_rnat4_out *rn, void *stream)
+{
+	return classify_v4_ct(c, t, n, now, verdict, ct_ret, identity, stage, nullptr, stream, rn);
 }
 
 CGPU_EXPORT int cgpu_classify_v4_ct(cgpu_ctx *c, const cgpu_tuples_v4_ct *t, size_t n, uint32_t now,
@@ -6399,8 +6608,8 @@ CGPU_EXPORT int cgpu_classify_v4_ct_tun(cgpu_ctx *c, const cgpu_tuples_v4_ct *t,
 	return classify_v4_ct(c, t, n, now, verdict, ct_ret, identity, stage, tunnel, stream);
 }
 
-CGPU_EXPORT int cgpu_classify_v4_ctlb(cgpu_ctx *c, const cgpu_tuples_v4_ct *t, const uint32_t *hash,
-				      size_t n, uint32_t now, const cgpu_ctlb_out *out, void *stream)
+static int classify_v4_ctlb(cgpu_ctx *c, const cgpu_tuples_v4_ct *t, const uint32_t *hash, size_t n,
+			    uint32_t now, const cgpu_ctlb_out *out, const cgpu_rnat4_out *rn, void *stream)
 {
 	Pinned P;
 	if (int r = pin(c, stream, P))
@@ -6432,11 +6641,25 @@ CGPU_EXPORT int cgpu_classify_v4_ctlb(cgpu_ctx *c, const cgpu_tuples_v4_ct *t, c
 	a.hash = hash;
 	a.n = n;
 	a.now = now;
-	return ct_classify(c, P.snap(), P.delta, c->ct4, a, stream, true);
+	rnat4_into(a, rn);
+	return ct_classify(c, P.snap(), P.delta, c->ct4, a, stream, true, rn != nullptr);
 }
 
-CGPU_EXPORT int cgpu_classify_v6_ctlb(cgpu_ctx *c, const cgpu_tuples_v6_ct *t, const uint32_t *hash,
-				      size_t n, uint32_t now, const cgpu_ctlb6_out *out, void *stream)
+CGPU_EXPORT int cgpu_classify_v4_ctlb(cgpu_ctx *c, const cgpu_tuples_v4_ct *t, const uint32_t *hash,
+				      size_t n, uint32_t now, const cgpu_ctlb_out *out, void *stream)
+{
+	return classify_v4_ctlb(c, t, hash, n, now, out, nullptr, stream);
+}
+
+CGPU_EXPORT int cgpu_classify_v4_ctlb_rnat(cgpu_ctx *c, const cgpu_tuples_v4_ct *t, const uint32_t *hash,
+					   size_t n, uint32_t now, const cgpu_ctlb_out *out,
+					   const cgpu_rnat4_out *rn, void *stream)
+{
+	return classify_v4_ctlb(c, t, hash, n, now, out, rn, stream);
+}
+
+static int classify_v6_ctlb(cgpu_ctx *c, const cgpu_tuples_v6_ct *t, const uint32_t *hash, size_t n,
+			    uint32_t now, const cgpu_ctlb6_out *out, const cgpu_rnat6_out *rn, void *stream)
 {
 	Pinned P;
 	if (int r = pin(c, stream, P))
@@ -6470,11 +6693,27 @@ CGPU_EXPORT int cgpu_classify_v6_ctlb(cgpu_ctx *c, const cgpu_tuples_v6_ct *t, c
 	a.hash = hash;
 	a.n = n;
 	a.now = now;
-	return ct_classify(c, P.snap(), P.delta, c->ct6, a, stream, true);
+	if (int r = rnat6_into(a, rn))
+		return r;
+	return ct_classify(c, P.snap(), P.delta, c->ct6, a, stream, true, rn != nullptr);
+}
+
+CGPU_EXPORT int cgpu_classify_v6_ctlb(cgpu_ctx *c, const cgpu_tuples_v6_ct *t, const uint32_t *hash,
+				      size_t n, uint32_t now, const cgpu_ctlb6_out *out, void *stream)
+{
+	return classify_v6_ctlb(c, t, hash, n, now, out, nullptr, stream);
+}
+
+CGPU_EXPORT int cgpu_classify_v6_ctlb_rnat(cgpu_ctx *c, const cgpu_tuples_v6_ct *t, const uint32_t *hash,
+					   size_t n, uint32_t now, const cgpu_ctlb6_out *out,
+					   const cgpu_rnat6_out *rn, void *stream)
+{
+	return classify_v6_ctlb(c, t, hash, n, now, out, rn, stream);
 }
 
 static int classify_v6_ct(cgpu_ctx *c, const cgpu_tuples_v6_ct *t, size_t n, uint32_t now, int32_t *verdict,
-			  uint8_t *ct_ret, uint32_t *identity, uint8_t *stage, uint32_t *tunnel, void *stream)
+			  uint8_t *ct_ret, uint32_t *identity, uint8_t *stage, uint32_t *tunnel, void *stream,
+			  const cgpu_rnat6_out *rn = nullptr)
 {
 	Pinned P;
 	if (int r = pin(c, stream, P))
@@ -6506,7 +6745,16 @@ static int classify_v6_ct(cgpu_ctx *c, const cgpu_tuples_v6_ct *t, size_t n, uin
 	a.now = now;
 	a.tunnel = tunnel;
 	a.tun = &P.tun();
-	return ct_classify(c, P.snap(), P.delta, c->ct6, a, stream);
+	if (int r = rnat6_into(a, rn))
+		return r;
+	return ct_classify(c, P.snap(), P.delta, c->ct6, a, stream, false, rn != nullptr);
+}
+
+CGPU_EXPORT int cgpu_classify_v6_ct_rnat(cgpu_ctx *c, const cgpu_tuples_v6_ct *t, size_t n, uint32_t now,
+					 int32_t *verdict, uint8_t *ct_ret, uint32_t *identity,
+					 uint8_t *stage, const cgpu_rnat6_out *rn, void *stream)
+{
+	return classify_v6_ct(c, t, n, now, verdict, ct_ret, identity, stage, nullptr, stream, rn);
 }
 
 CGPU_EXPORT int cgpu_classify_v6_ct(cgpu_ctx *c, const cgpu_tuples_v6_ct *t, size_t n, uint32_t now,
@@ -6536,7 +6784,9 @@ CGPU_EXPORT int cgpu_classify_v6_ct_tun(cgpu_ctx *c, const cgpu_tuples_v6_ct *t,
  * calls the agent uses.  File: "CGPUMIR1", u32 version, u32 section count,
  * sections {u32 tag, u32 record bytes, u64 count, records}, then the FNV-1a
  * hash of everything before it. */
-enum { MIR_IPC = 1, MIR_POL, MIR_CIDR, MIR_EP, MIR_LB4, MIR_LB6, MIR_LXC, MIR_REV, MIR_CT4, MIR_CT6 };
+enum { MIR_IPC = 1, MIR_POL, MIR_CIDR, MIR_EP, MIR_LB4, MIR_LB6, MIR_LXC, MIR_REV, MIR_CT4, MIR_CT6,
+       MIR_RN4, MIR_RN6, /* {u16 index, value}: 8 / 20 B; absent from files written before they existed */
+       MIR_LAST = MIR_RN6 };
 
 struct MirOut {
 	std::vector<uint8_t> buf;
@@ -6585,7 +6835,7 @@ CGPU_EXPORT int cgpu_mirror_save(cgpu_ctx *c, const char *path)
 	MirOut o;
 	o.put("CGPUMIR1", 8);
 	o.put((uint32_t)1);
-	o.put((uint32_t)10);
+	o.put((uint32_t)12);
 	{
 		std::lock_guard<std::mutex> g(c->mu);
 		/* device-side state the mirror does not hold: per-entry counters
@@ -6668,6 +6918,18 @@ CGPU_EXPORT int cgpu_mirror_save(cgpu_ctx *c, const char *path)
 		o.count(at, 1);
 		mir_ct(o, MIR_CT4, c->ct4, 14);
 		mir_ct(o, MIR_CT6, c->ct6, 38);
+		at = o.section(MIR_RN4, 8);
+		for (auto &kv : c->rn4) {
+			o.put(kv.first);
+			o.put(kv.second);
+		}
+		o.count(at, c->rn4.size());
+		at = o.section(MIR_RN6, 20);
+		for (auto &kv : c->rn6) {
+			o.put(kv.first);
+			o.put(kv.second);
+		}
+		o.count(at, c->rn6.size());
 	}
 	o.put(fnv(1469598103934665603ull, o.buf.data(), o.buf.size()));
 	const std::string tmp = std::string(path) + ".tmp";
@@ -6773,6 +7035,16 @@ static void mirror_rollback(cgpu_ctx *c, const std::vector<uint8_t> &buf, const 
 				cgpu_ct6_delete(c, &key);
 				break;
 			}
+			case MIR_RN4:
+			case MIR_RN6: {
+				uint16_t index;
+				memcpy(&index, r, 2);
+				if (s_.tag == MIR_RN4)
+					cgpu_revnat4_delete(c, index);
+				else
+					cgpu_revnat6_delete(c, index);
+				break;
+			}
 			}
 		}
 	}
@@ -6808,7 +7080,7 @@ CGPU_EXPORT int cgpu_mirror_restore(cgpu_ctx *c, const char *path)
 		std::lock_guard<std::mutex> g(c->mu);
 		bool empty = c->ipc.empty() && !c->pol_total && c->dyn4.empty() && c->dyn6.empty() &&
 			     c->fix4.empty() && c->fix6.empty() && c->lxc.empty() && c->lb.empty() &&
-			     c->lb6.empty() && c->lxcinfo.empty();
+			     c->lb6.empty() && c->lxcinfo.empty() && c->rn4.empty() && c->rn6.empty();
 		for (CtMap *m : {&c->ct4, &c->ct6}) {
 			if (int r = ct_pull(c, *m))
 				return r;
@@ -6822,7 +7094,7 @@ CGPU_EXPORT int cgpu_mirror_restore(cgpu_ctx *c, const char *path)
 	std::vector<Sec> secs;
 	size_t off = 16;
 	const size_t end = buf.size() - 8;
-	static const uint32_t recsz[] = {0, 32, 36, 24, 20, 20, 44, 36, 8, 70, 94};
+	static const uint32_t recsz[] = {0, 32, 36, 24, 20, 20, 44, 36, 8, 70, 94, 8, 20};
 	for (uint32_t i = 0; i < nsec; i++) {
 		Sec s_;
 		if (off + 16 > end)
@@ -6831,7 +7103,7 @@ CGPU_EXPORT int cgpu_mirror_restore(cgpu_ctx *c, const char *path)
 		memcpy(&s_.rec, &buf[off + 4], 4);
 		memcpy(&s_.n, &buf[off + 8], 8);
 		s_.off = off + 16;
-		if (s_.tag < MIR_IPC || s_.tag > MIR_CT6 || s_.rec != recsz[s_.tag] ||
+		if (s_.tag < MIR_IPC || s_.tag > MIR_LAST || s_.rec != recsz[s_.tag] ||
 		    s_.n > (end - s_.off) / s_.rec)
 			return fail(-EINVAL, "%s: bad section %u", path, s_.tag);
 		off = s_.off + s_.n * s_.rec;
@@ -6843,7 +7115,7 @@ CGPU_EXPORT int cgpu_mirror_restore(cgpu_ctx *c, const char *path)
 	 * context configured smaller than the one that saved the file is refused
 	 * before anything is applied */
 	{
-		uint64_t cnt[MIR_CT6 + 1] = {};
+		uint64_t cnt[MIR_LAST + 1] = {};
 		std::map<uint32_t, uint64_t> per_ep;
 		for (const Sec &s_ : secs) {
 			cnt[s_.tag] += s_.n;
@@ -6861,7 +7133,9 @@ CGPU_EXPORT int cgpu_mirror_restore(cgpu_ctx *c, const char *path)
 			const char *what;
 		} lim[] = {{MIR_IPC, cap.ipcache, "ipcache_max"},   {MIR_EP, cap.endpoints, "endpoints_max"},
 			   {MIR_LB4, cap.lb, "lb_max_entries (lb4)"}, {MIR_LB6, cap.lb, "lb_max_entries (lb6)"},
-			   {MIR_CT4, cap.ct4, "ct_max"},              {MIR_CT6, cap.ct6, "ct6_max"}};
+			   {MIR_CT4, cap.ct4, "ct_max"},              {MIR_CT6, cap.ct6, "ct6_max"},
+			   {MIR_RN4, cap.lb, "lb_max_entries (reverse NAT 4)"},
+			   {MIR_RN6, cap.lb, "lb_max_entries (reverse NAT 6)"}};
 		for (const auto &l : lim)
 			if (cnt[l.tag] > l.max)
 				return fail(-E2BIG, "%s: %llu records exceed this context's %s (%llu)", path,
@@ -6961,6 +7235,22 @@ CGPU_EXPORT int cgpu_mirror_restore(cgpu_ctx *c, const char *path)
 				memcpy(&k, r, 38);
 				memcpy(&v, r + 38, 56);
 				rc = cgpu_ct6_update(c, &k, &v, CGPU_NOEXIST);
+				break;
+			}
+			case MIR_RN4: {
+				uint16_t index;
+				cgpu_lb4_reverse_nat v;
+				memcpy(&index, r, 2);
+				memcpy(&v, r + 2, 6);
+				rc = cgpu_revnat4_update(c, index, &v, CGPU_NOEXIST);
+				break;
+			}
+			case MIR_RN6: {
+				uint16_t index;
+				cgpu_lb6_reverse_nat v;
+				memcpy(&index, r, 2);
+				memcpy(&v, r + 2, 18);
+				rc = cgpu_revnat6_update(c, index, &v, CGPU_NOEXIST);
 				break;
 			}
 			}

@@ -5039,6 +5039,10 @@ struct ct_args {
 	uint8_t *pcls;               /* [n] service path: phase-2 class, PCL_* (k_ct_prep) */
 	uint64_t *pk;                /* packed per-slot counters (k_ct_finish, k_unpack) */
 	uint32_t dflt; /* nonzero: group-default results (CGPU_CT_DFLT) */
+	/* the _rnat entry points: [n] per packet, zeroed before the walks; a walker
+	 * compiled with RN stores rev_nat_index | lb_loopback << 16 of the entry a
+	 * packet hit when that index is nonzero (k_ct_rnat reads it) */
+	uint32_t *rn;
 };
 
 /* One packet's record, written by k_ct_prep{,6} and read by the walker and
@@ -6431,9 +6435,10 @@ template <class K> __device__ __forceinline__ ct_row ct_new_row(const ct_pkt &q,
  * :288-412) and ct_create4 / ct_create6 (:653-744 / :588-639), with the
  * policy outcome of the endpoint programs (bpf_lxc.c:506-537 / :918-937,
  * :192-203 / :776-800).  k = the reply-direction tuple of the first lookup. */
-template <class K>
+template <class K, bool RN = false>
 __device__ __forceinline__ uint32_t ct_step(const ct_table &T, const ct_acct &A, ct_cache<K> &c,
-					   typename K::key k, const ct_pkt &q, uint32_t now)
+					   typename K::key k, const ct_pkt &q, uint32_t now,
+					   uint32_t *rn = nullptr)
 {
 	const uint32_t meta = q.meta;
 	const bool ingress = !(meta & CTM_EGRESS);
@@ -6457,6 +6462,8 @@ __device__ __forceinline__ uint32_t ct_step(const ct_table &T, const ct_acct &A,
 	}
 	if (ret != CT_NEW) {
 		ct_row e = ctc_row(c, ci);
+		if constexpr (RN) /* ct_state of the hit entry (conntrack.h ct_lookup: rev_nat_index, loopback) */
+			*rn = (e.c.y >> 16) | ((e.c.y & CTB_LB_LOOPBACK) ? 0x10000u : 0u);
 		ct_hit(e, meta, ingress, q.w, q.len, now);
 		ctc_put(c, ci, ctc_pos(c, ci), e);
 	}
@@ -6906,7 +6913,7 @@ extern "C" __attribute__((visibility("default"))) int cgpu_diag_walk_clock(unsig
 }
 #endif
 
-template <class K, int MODE>
+template <class K, int MODE, bool RN = false>
 __global__ __launch_bounds__(256, K::ADDR ? CGPU_WALK_MINB_SVC : CGPU_WALK_W) void k_ct_walk(cgpu_snapshot s, ct_table T, ct_args a)
 {
 #ifdef CGPU_DIAG_WALK_CLOCK
@@ -7033,7 +7040,15 @@ __global__ __launch_bounds__(256, K::ADDR ? CGPU_WALK_MINB_SVC : CGPU_WALK_W) vo
 				}
 				if (MODE == WALK_PKT && (meta & CTM_PHASE2))
 					continue;
-				const uint32_t ret = ct_step<K>(T, A, c, r.key(), q, a.now);
+				uint32_t rnw = 0;
+				const uint32_t ret = ct_step<K, RN>(T, A, c, r.key(), q, a.now, &rnw);
+				if constexpr (RN) {
+					/* before the orientation default skips the result store:
+					 * whatever the entry came from (the map or this lane's
+					 * cache), a nonzero index reaches the side array */
+					if (rnw & 0xFFFFu)
+						a.rn[i] = rnw;
+				}
 #ifdef CGPU_DIAG_RET_DEFAULT /* timing only: no store where the result is the direction's default */
 				if (ret == ((meta & CTM_EGRESS) ? CT_ESTABLISHED : CT_REPLY))
 					continue;
@@ -7482,6 +7497,7 @@ static ct_args ct_args_of(const ct_launch &L)
 	a.pcls = L.pcls;
 	a.pk = L.pk;
 	a.dflt = L.dflt;
+	a.rn = L.rn;
 	return a;
 }
 
@@ -7688,6 +7704,112 @@ template <class K> static hipError_t launch_ct_finish(const cgpu_snapshot &s, co
 	return hipSuccess;
 }
 
+/* the conntrack walks (WALK_PKT, WALK_OWED): the RN instantiation only for
+ * the _rnat entry points (a.rn set), so the others run the kernels they ran */
+template <class K, int MODE>
+static void launch_ct_walk(const cgpu_snapshot &s, const ct_table &T, const ct_args &a, hipStream_t st)
+{
+	if (a.rn)
+		hipLaunchKernelGGL((k_ct_walk<K, MODE, true>), dim3(CT_WALK_GRID), dim3(256), 0, st, s, T, a);
+	else
+		hipLaunchKernelGGL((k_ct_walk<K, MODE>), dim3(CT_WALK_GRID), dim3(256), 0, st, s, T, a);
+}
+
+/* Reverse NAT of the replies (cgpu_classify_v{4,6}_ct{,lb}_rnat), after the
+ * finish: per packet in batch order the frame's source (and IPv4 destination)
+ * as the endpoint program leaves it.  The frame starts as the input, on the
+ * service paths as lb4_xlate / lb6_xlate left it (svc_out: daddr := the
+ * backend, IPv4 saddr := IPV4_LOOPBACK when the backend is the sender,
+ * lb.h:654-697, :761-766).  Where the call site's condition holds
+ *   IPv4 egress  bpf_lxc.c:531-541  ct_ret REPLY / RELATED, rev_nat_index
+ *   IPv4 ingress bpf_lxc.c:909-918  ct_ret REPLY, rev_nat_index, !loopback
+ *   IPv6 egress  bpf_lxc.c:222-235  ct_ret REPLY / RELATED, rev_nat_index
+ *   IPv6 ingress bpf_lxc.c:778-785  any hit with rev_nat_index
+ * the index (a.rn, from the walker) is looked up in the dense table; a
+ * present row is __lb4_rev_nat / __lb6_rev_nat (lb.h:485-550 / :254-294): the
+ * source port of a TCP / UDP frame := nat->port unless 0
+ * (reverse_map_l4_port, :218-252), IPv4 daddr := the old saddr when the
+ * entry's lb_loopback is set, saddr := nat->address. */
+struct rnat_args {
+	const uint2 *t4; /* [65536] {address, port | 1 << 16} or NULL (empty map) */
+	const uint4 *t6; /* [65536][2] {address}, {port | 1 << 16, 0, 0, 0} or NULL */
+	uint32_t *saddr, *daddr; /* outputs, any NULL (IPv6: saddr 16 bytes per packet) */
+	uint16_t *sport;
+	uint8_t *applied;
+};
+
+template <class K> __global__ __launch_bounds__(256) void k_ct_rnat(ct_args a, rnat_args r, uint32_t loopback)
+{
+	const uint64_t stride = (uint64_t)gridDim.x * 256u;
+	for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < a.n; i += stride) {
+		const bool egress = a.flags[i] & 1u;
+		const uint32_t pr = a.proto[i], cr = a.ct_ret[i], w = a.rn[i];
+		const uint32_t idx = w & 0xFFFFu;
+		[[maybe_unused]] const bool lo = (w >> 16) & 1u;
+		uint32_t sp = a.sport[i], applied = 0;
+		const bool l4 = pr == 6u || pr == 17u;
+		if constexpr (K::V6 != 0) {
+			uint4 sa = reinterpret_cast<const uint4 *>(a.saddr)[i];
+			const bool go = idx && (egress ? (cr == CT_REPLY || cr == CT_RELATED) : (cr >= CT_ESTABLISHED && cr <= CT_RELATED));
+			if (go && r.t6) {
+				const uint4 e = r.t6[2u * idx + 1u];
+				if (e.x >> 16) {
+					applied = 1;
+					if ((e.x & 0xFFFFu) && l4)
+						sp = e.x & 0xFFFFu;
+					sa = r.t6[2u * idx];
+				}
+			}
+			if (r.saddr)
+				reinterpret_cast<uint4 *>(r.saddr)[i] = sa;
+		} else {
+			uint32_t sa = a.saddr[i], da = a.daddr[i];
+			if constexpr (K::SVC) {
+				if (egress) {
+					const uint4 so = a.svc_out[i];
+					if ((so.x & 3u) == SVC_XLATED) {
+						da = so.y;
+						if ((so.x >> 8) & LBS_SNAT)
+							sa = loopback;
+					}
+				}
+			}
+			const bool go = idx && (egress ? (cr == CT_REPLY || cr == CT_RELATED) : (cr == CT_REPLY && !lo));
+			if (go && r.t4) {
+				const uint2 e = r.t4[idx];
+				if (e.y >> 16) {
+					applied = 1;
+					if ((e.y & 0xFFFFu) && l4)
+						sp = e.y & 0xFFFFu;
+					if (lo)
+						da = sa;
+					sa = e.x;
+				}
+			}
+			if (r.saddr)
+				r.saddr[i] = sa;
+			if (r.daddr)
+				r.daddr[i] = da;
+		}
+		if (r.sport)
+			r.sport[i] = (uint16_t)sp;
+		if (r.applied)
+			r.applied[i] = (uint8_t)applied;
+	}
+}
+
+template <class K>
+static hipError_t launch_ct_rnat(const cgpu_snapshot &s, const ct_launch &L, const ct_args &a, hipStream_t st)
+{
+	if (!L.rn)
+		return hipSuccess;
+	const rnat_args r{static_cast<const uint2 *>(L.rn_t4), static_cast<const uint4 *>(L.rn_t6),
+			  static_cast<uint32_t *>(L.rn_saddr), L.rn_daddr, L.rn_sport, L.rn_applied};
+	const unsigned g = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((L.n + 255) / 256, 8192));
+	hipLaunchKernelGGL(k_ct_rnat<K>, dim3(g), dim3(256), 0, st, a, r, s.ipv4_loopback);
+	return hipGetLastError();
+}
+
 /* phase 2 of the plain paths (and of the IPv6 service path): the ICMP
  * errors and the owed ICMP entries of the creates, grouped by address pair,
  * in batch order (the prep and the walk set the candidate flags) */
@@ -7709,7 +7831,7 @@ static hipError_t ct_phase2(const cgpu_snapshot &s, const ct_table &T, const ct_
 	e = ct_group_sort(s, L, a, m, &nh, st, K::V6 != 0);
 	if (e != hipSuccess)
 		return e;
-	hipLaunchKernelGGL((k_ct_walk<K, WALK_OWED>), dim3(CT_WALK_GRID), dim3(256), 0, st, s, T, a);
+	launch_ct_walk<K, WALK_OWED>(s, T, a, st);
 	return hipGetLastError();
 }
 
@@ -7770,10 +7892,12 @@ static hipError_t launch_ct(const cgpu_snapshot &s, const ct_table &T, const ct_
 	hipError_t e = ct_group_sort(s, L, a, L.n, &nh, st, K::V6 != 0);
 	if (e != hipSuccess)
 		return e;
-	hipLaunchKernelGGL((k_ct_walk<K, WALK_PKT>), dim3(CT_WALK_GRID), dim3(256), 0, st, s, T, a);
+	launch_ct_walk<K, WALK_PKT>(s, T, a, st);
 	if ((e = ct_phase2<K>(s, T, L, a, st)) != hipSuccess)
 		return e;
-	return launch_ct_finish<K>(s, a, st);
+	if ((e = launch_ct_finish<K>(s, a, st)) != hipSuccess)
+		return e;
+	return launch_ct_rnat<K>(s, L, a, st);
 }
 
 hipError_t launch_classify_v4_ct(const cgpu_snapshot &s, const ct_table &T, const ct_launch &L,
@@ -7849,10 +7973,12 @@ hipError_t launch_classify_v6_ctlb(const cgpu_snapshot &s, const ct_table &T, co
 	e = ct_group_sort(s, L, a, L.n, &nh, st, true);
 	if (e != hipSuccess)
 		return e;
-	hipLaunchKernelGGL((k_ct_walk<CtK6S, WALK_PKT>), dim3(CT_WALK_GRID), dim3(256), 0, st, s, T, a);
+	launch_ct_walk<CtK6S, WALK_PKT>(s, T, a, st);
 	if ((e = ct_phase2<CtK6S>(s, T, L, a, st)) != hipSuccess)
 		return e;
-	return launch_ct_finish<CtK6S>(s, a, st);
+	if ((e = launch_ct_finish<CtK6S>(s, a, st)) != hipSuccess)
+		return e;
+	return launch_ct_rnat<CtK6S>(s, L, a, st);
 }
 
 /*
@@ -7908,7 +8034,7 @@ hipError_t launch_classify_v4_ctlb(const cgpu_snapshot &s, const ct_table &T, co
 	e = ct_group_sort(s, L, a, L.n, &nh, st);
 	if (e != hipSuccess)
 		return e;
-	hipLaunchKernelGGL((k_ct_walk<CtK4S, WALK_PKT>), dim3(CT_WALK_GRID), dim3(256), 0, st, s, T, a);
+	launch_ct_walk<CtK4S, WALK_PKT>(s, T, a, st);
 	if (!serial && (ctl[1] || ctl[2])) {
 		const unsigned g2 = (unsigned)std::min<uint64_t>((L.n + 255) / 256, 8192);
 		for (uint32_t ph = 0; ph < 2u; ph++) {
@@ -7939,10 +8065,12 @@ hipError_t launch_classify_v4_ctlb(const cgpu_snapshot &s, const ct_table &T, co
 			e = ct_group_sort(s, L, a, m, &nh, st);
 			if (e != hipSuccess)
 				return e;
-			hipLaunchKernelGGL((k_ct_walk<CtK4S, WALK_OWED>), dim3(CT_WALK_GRID), dim3(256), 0, st, s, T, a);
+			launch_ct_walk<CtK4S, WALK_OWED>(s, T, a, st);
 		}
 	}
-	return launch_ct_finish<CtK4S>(s, a, st);
+	if ((e = launch_ct_finish<CtK4S>(s, a, st)) != hipSuccess)
+		return e;
+	return launch_ct_rnat<CtK4S>(s, L, a, st);
 }
 
 /* ======================================================================= */

@@ -186,6 +186,17 @@ struct ct_launch {
 	 * the tunnel tables `tun` (plain paths only) */
 	uint32_t *tunnel;
 	const ipc_tun *tun;
+	/* cgpu_classify_v{4,6}_ct{,lb}_rnat: rn != NULL selects the walkers that
+	 * fill it ([n] scratch, zeroed by the caller before the launch: the hit
+	 * entry's rev_nat_index | lb_loopback << 16) and the rewrite kernel after
+	 * the finish; the dense reverse-NAT tables (NULL: that map is empty) and
+	 * the outputs (any NULL; IPv6 rn_saddr 16 bytes per packet, no rn_daddr) */
+	uint32_t *rn;
+	const void *rn_t4, *rn_t6;
+	void *rn_saddr;
+	uint32_t *rn_daddr;
+	uint16_t *rn_sport;
+	uint8_t *rn_applied;
 };
 
 size_t ct_temp_bytes(uint64_t n);

@@ -25,8 +25,8 @@ import ipaddress
 import numpy as np
 
 from . import layouts as L
-from ._abi import (CgpuConfig, CgpuError, CtlbOut, FrameTuples, Frames, Lb4Out, Lb4Tuples, TuplesV4,
-                   TuplesV4Ct, TuplesV6Ct, TuplesV6, check, lib)
+from ._abi import (CgpuConfig, CgpuError, CtlbOut, FrameTuples, Frames, Lb4Out, Lb4Tuples, Rnat4Out,
+                   Rnat6Out, TuplesV4, TuplesV4Ct, TuplesV6Ct, TuplesV6, check, lib)
 
 CIDR_V4_DYN, CIDR_V4_FIX, CIDR_V6_DYN, CIDR_V6_FIX = 0, 1, 2, 3
 BPF_ANY, BPF_NOEXIST, BPF_EXIST = 0, 1, 2
@@ -259,6 +259,65 @@ class Engine:
 
     def lb6_count(self) -> int:
         return self.L.cgpu_lb6_count(self.h)
+
+    # --- cilium_lb4_reverse_nat / cilium_lb6_reverse_nat (index: the raw u16 key) ---
+    def _revnat_keys(self, fn):
+        keys, prev = [], None
+        out = C.c_uint16()
+        while fn(self.h, prev, C.byref(out)) == 0:
+            keys.append(int(out.value))
+            prev = C.byref(C.c_uint16(out.value))
+        return keys
+
+    def revnat4_update(self, index: int, val, flags=BPF_ANY) -> int:
+        return self.L.cgpu_revnat4_update(self.h, index, _buf(val), flags)
+
+    def revnat4_delete(self, index: int) -> int:
+        return self.L.cgpu_revnat4_delete(self.h, index)
+
+    def revnat4_lookup(self, index: int):
+        out = C.create_string_buffer(6)
+        rc = self.L.cgpu_revnat4_lookup(self.h, index, out)
+        return rc, (np.frombuffer(out.raw, L.LB4_REVERSE_NAT)[0] if rc == 0 else None)
+
+    def revnat4_keys(self):
+        return self._revnat_keys(self.L.cgpu_revnat4_get_next_key)
+
+    def revnat4_count(self) -> int:
+        return self.L.cgpu_revnat4_count(self.h)
+
+    def revnat6_update(self, index: int, val, flags=BPF_ANY) -> int:
+        return self.L.cgpu_revnat6_update(self.h, index, _buf(val), flags)
+
+    def revnat6_delete(self, index: int) -> int:
+        return self.L.cgpu_revnat6_delete(self.h, index)
+
+    def revnat6_lookup(self, index: int):
+        out = C.create_string_buffer(18)
+        rc = self.L.cgpu_revnat6_lookup(self.h, index, out)
+        return rc, (np.frombuffer(out.raw, L.LB6_REVERSE_NAT)[0] if rc == 0 else None)
+
+    def revnat6_keys(self):
+        return self._revnat_keys(self.L.cgpu_revnat6_get_next_key)
+
+    def revnat6_count(self) -> int:
+        return self.L.cgpu_revnat6_count(self.h)
+
+    def UpdateRevNat(self, index: int, vip: str, port: int):  # noqa: N802
+        """lbmap.UpdateRevNat (lbmap.go:229-244): reverse-NAT entry `index`
+        (host order, as UpdateService's rev_nat) -> {vip, port}; the family
+        follows the address."""
+        if ipaddress.ip_address(vip).version == 4:
+            check(self.revnat4_update(L.revnat_index(index), L.lb4_reverse_nat(vip, port)), "UpdateRevNat")
+        else:
+            check(self.revnat6_update(L.revnat_index(index), L.lb6_reverse_nat(vip, port)), "UpdateRevNat")
+
+    def DeleteRevNat(self, index: int, v6: bool = False):  # noqa: N802
+        """lbmap.DeleteRevNat (lbmap.go:246-260)."""
+        fn = self.revnat6_delete if v6 else self.revnat4_delete
+        rc = fn(L.revnat_index(index))
+        if rc != 0:
+            raise CgpuError(errno.ENOENT, f"reverse NAT index {index} not found")
 
     def flow_hash6(self, saddr16, daddr16, sport, dport, proto) -> int:
         return self.L.cgpu_flow_hash6(bytes(saddr16), bytes(daddr16), sport, dport, proto)
@@ -548,12 +607,17 @@ class Engine:
         return out
 
     def classify_v4_ct(self, t: dict, now: int, out: dict | None = None, stage: bool = True,
-                       stream=None, tunnel: bool = False):
+                       stream=None, tunnel: bool = False, rev_nat: bool = False):
         """Stateful classification (cgpu_classify_v4_ct): t holds CUDA tensors
         saddr/daddr (int32), sport/dport (int16, network order), proto/flags
         (uint8), l4b (int16: TCP header bytes 12-13 / ICMP type), len (int32),
         ep (int16); now = bpf_ktime_get_sec() of the batch.
-        tunnel=True: out["tunnel"] too (_ct_tun)."""
+        tunnel=True: out["tunnel"] too (_ct_tun).  rev_nat=True
+        (cgpu_classify_v4_ct_rnat): out["rn_saddr"], ["rn_daddr"] (int32),
+        ["rn_sport"] (int16), ["rn_applied"] (uint8), the frame after the
+        replies' reverse NAT."""
+        if tunnel and rev_nat:
+            raise ValueError("tunnel and rev_nat cannot be combined")
         if tunnel:
             return self._ct_tun(False, t, now, out, stage, stream)
         import torch
@@ -566,14 +630,39 @@ class Engine:
                    "stage": torch.empty(n, dtype=torch.uint8, device=dev) if stage else None}
         tv = TuplesV4Ct(*[t[k].data_ptr() for k in
                           ("saddr", "daddr", "sport", "dport", "proto", "l4b", "flags", "len", "ep")])
+        if rev_nat:
+            rn = self._rnat_out(False, out, n, dev)
+            check(self.L.cgpu_classify_v4_ct_rnat(self.h, C.byref(tv), n, now, _ptr(out["verdict"]),
+                                                  _ptr(out["ct_ret"]), _ptr(out["identity"]),
+                                                  _ptr(out.get("stage")), C.byref(rn), _stream(stream)),
+                  "cgpu_classify_v4_ct_rnat")
+            return out
         check(self.L.cgpu_classify_v4_ct(self.h, C.byref(tv), n, now, _ptr(out["verdict"]),
                                          _ptr(out["ct_ret"]), _ptr(out["identity"]),
                                          _ptr(out.get("stage")), _stream(stream)),
               "cgpu_classify_v4_ct")
         return out
 
+    @staticmethod
+    def _rnat_out(v6: bool, out: dict, n: int, dev):
+        """The rev_nat=True outputs into `out` (allocated unless given) and
+        their cgpu_rnat4_out / cgpu_rnat6_out."""
+        import torch
+        if out.get("rn_saddr") is None:
+            out["rn_saddr"] = torch.empty((n, 16), dtype=torch.uint8, device=dev) if v6 else \
+                torch.empty(n, dtype=torch.int32, device=dev)
+        if not v6 and out.get("rn_daddr") is None:
+            out["rn_daddr"] = torch.empty(n, dtype=torch.int32, device=dev)
+        if out.get("rn_sport") is None:
+            out["rn_sport"] = torch.empty(n, dtype=torch.int16, device=dev)
+        if out.get("rn_applied") is None:
+            out["rn_applied"] = torch.empty(n, dtype=torch.uint8, device=dev)
+        if v6:
+            return Rnat6Out(*[out[k].data_ptr() for k in ("rn_saddr", "rn_sport", "rn_applied")])
+        return Rnat4Out(*[out[k].data_ptr() for k in ("rn_saddr", "rn_daddr", "rn_sport", "rn_applied")])
+
     def classify_v4_ctlb(self, t: dict, now: int, out: dict | None = None, stage: bool = True,
-                         xlate: bool = True, stream=None):
+                         xlate: bool = True, stream=None, rev_nat: bool = False):
         """cgpu_classify_v4_ctlb: classify_v4_ct with the stateful service
         step (lb4_local with CONNTRACK) in front; t may carry a "hash" column
         (skb->hash, int32).  out adds "daddr" / "dport": the frame after the
@@ -592,14 +681,23 @@ class Engine:
                           ("saddr", "daddr", "sport", "dport", "proto", "l4b", "flags", "len", "ep")])
         ov = CtlbOut(*[_ptr(out.get(k)) for k in ("verdict", "ct_ret", "identity", "stage", "daddr",
                                                    "dport")])
+        if rev_nat:  # cgpu_classify_v4_ctlb_rnat: out["rn_*"] as classify_v4_ct
+            rn = self._rnat_out(False, out, n, dev)
+            check(self.L.cgpu_classify_v4_ctlb_rnat(self.h, C.byref(tv), _ptr(t.get("hash")), n, now,
+                                                    C.byref(ov), C.byref(rn), _stream(stream)),
+                  "cgpu_classify_v4_ctlb_rnat")
+            return out
         check(self.L.cgpu_classify_v4_ctlb(self.h, C.byref(tv), _ptr(t.get("hash")), n, now,
                                            C.byref(ov), _stream(stream)), "cgpu_classify_v4_ctlb")
         return out
 
     def classify_v6_ct(self, t: dict, now: int, out: dict | None = None, stage: bool = True,
-                       stream=None, tunnel: bool = False):
+                       stream=None, tunnel: bool = False, rev_nat: bool = False):
         """cgpu_classify_v6_ct: as classify_v4_ct with saddr / daddr (n, 16)
-        uint8 tensors (16-byte aligned rows)."""
+        uint8 tensors (16-byte aligned rows).  rev_nat=True: out["rn_saddr"]
+        (n, 16) uint8, ["rn_sport"], ["rn_applied"] (IPv6 has no rn_daddr)."""
+        if tunnel and rev_nat:
+            raise ValueError("tunnel and rev_nat cannot be combined")
         if tunnel:
             return self._ct_tun(True, t, now, out, stage, stream)
         import torch
@@ -612,6 +710,13 @@ class Engine:
                    "stage": torch.empty(n, dtype=torch.uint8, device=dev) if stage else None}
         tv = TuplesV6Ct(*[t[k].data_ptr() for k in
                           ("saddr", "daddr", "sport", "dport", "proto", "l4b", "flags", "len", "ep")])
+        if rev_nat:
+            rn = self._rnat_out(True, out, n, dev)
+            check(self.L.cgpu_classify_v6_ct_rnat(self.h, C.byref(tv), n, now, _ptr(out["verdict"]),
+                                                  _ptr(out["ct_ret"]), _ptr(out["identity"]),
+                                                  _ptr(out.get("stage")), C.byref(rn), _stream(stream)),
+                  "cgpu_classify_v6_ct_rnat")
+            return out
         check(self.L.cgpu_classify_v6_ct(self.h, C.byref(tv), n, now, _ptr(out["verdict"]),
                                          _ptr(out["ct_ret"]), _ptr(out["identity"]),
                                          _ptr(out.get("stage")), _stream(stream)),
@@ -619,7 +724,7 @@ class Engine:
         return out
 
     def classify_v6_ctlb(self, t: dict, now: int, out: dict | None = None, stage: bool = True,
-                         xlate: bool = True, stream=None):
+                         xlate: bool = True, stream=None, rev_nat: bool = False):
         """cgpu_classify_v6_ctlb: classify_v6_ct with the stateful service
         step (lb6_local with CONNTRACK) in front; out "daddr" is (n, 16)
         uint8."""
@@ -637,6 +742,12 @@ class Engine:
                           ("saddr", "daddr", "sport", "dport", "proto", "l4b", "flags", "len", "ep")])
         ov = CtlbOut(*[_ptr(out.get(k)) for k in ("verdict", "ct_ret", "identity", "stage", "daddr",
                                                    "dport")])
+        if rev_nat:  # cgpu_classify_v6_ctlb_rnat: out["rn_*"] as classify_v6_ct
+            rn = self._rnat_out(True, out, n, dev)
+            check(self.L.cgpu_classify_v6_ctlb_rnat(self.h, C.byref(tv), _ptr(t.get("hash")), n, now,
+                                                    C.byref(ov), C.byref(rn), _stream(stream)),
+                  "cgpu_classify_v6_ctlb_rnat")
+            return out
         check(self.L.cgpu_classify_v6_ctlb(self.h, C.byref(tv), _ptr(t.get("hash")), n, now,
                                            C.byref(ov), _stream(stream)), "cgpu_classify_v6_ctlb")
         return out
@@ -1104,6 +1215,12 @@ class LBMap:
                                 L.lb4_service(0, 0, len(backends), 0, nonzero)), "UpdateService")
         for s in range(len(backends) + 1, existing + 1):
             self.e.lb4_delete(L.lb4_key(vip, port, s))
+
+    def UpdateRevNat(self, index: int, vip: str, port: int):  # noqa: N802
+        self.e.UpdateRevNat(index, vip, port)
+
+    def DeleteRevNat(self, index: int, v6: bool = False):  # noqa: N802
+        self.e.DeleteRevNat(index, v6)
 
     def DeleteService(self, vip: str, port: int):  # noqa: N802
         rc, old = self.e.lb4_lookup(L.lb4_key(vip, port, 0))

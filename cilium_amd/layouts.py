@@ -50,6 +50,10 @@ LB6_KEY = np.dtype([("address", "u1", 16), ("dport", "<u2"), ("slave", "<u2")])
 LB6_SERVICE = np.dtype([("target", "u1", 16), ("port", "<u2"), ("count", "<u2"),
                         ("rev_nat_index", "<u2"), ("weight", "<u2")])
 assert LB6_KEY.itemsize == 20 and LB6_SERVICE.itemsize == 24
+# struct lb4_reverse_nat / lb6_reverse_nat (bpf/lib/common.h:441-444 / :422-425), packed
+LB4_REVERSE_NAT = np.dtype([("address", "<u4"), ("port", "<u2")])
+LB6_REVERSE_NAT = np.dtype([("address", "u1", 16), ("port", "<u2")])
+assert LB4_REVERSE_NAT.itemsize == 6 and LB6_REVERSE_NAT.itemsize == 18
 assert LPM_V4_KEY.itemsize == 8 and LPM_V6_KEY.itemsize == 20
 assert ENDPOINT_KEY.itemsize == 20
 
@@ -276,3 +280,27 @@ def lb4_service(target: str | int = 0, port_host: int = 0, count: int = 0, rev_n
     v["rev_nat_index"] = htons(rev_nat)
     v["weight"] = htons(weight)
     return v
+
+
+def lb4_reverse_nat(addr: str | int, port_host: int = 0) -> np.ndarray:
+    """lbmap.NewRevNat4Value(ip, port).ToNetwork(): the service address and
+    port a reply's source is rewritten to."""
+    v = np.zeros((), LB4_REVERSE_NAT)
+    v["address"] = ip4_be(addr)
+    v["port"] = htons(port_host)
+    return v
+
+
+def lb6_reverse_nat(addr: str | bytes, port_host: int = 0) -> np.ndarray:
+    """lbmap.NewRevNat6Value(ip, port).ToNetwork()."""
+    v = np.zeros((), LB6_REVERSE_NAT)
+    raw = ipaddress.ip_address(addr).packed if isinstance(addr, str) else bytes(addr)
+    v["address"][:] = np.frombuffer(raw, np.uint8)
+    v["port"] = htons(port_host)
+    return v
+
+
+def revnat_index(index_host: int) -> int:
+    """The raw map key of reverse-NAT index `index_host`: RevNat4Key.ToNetwork()
+    byte-swaps it, as lb4_service(...)["rev_nat_index"] holds it."""
+    return htons(index_host)

@@ -372,6 +372,45 @@ int cgpu_lb6_lookup(cgpu_ctx *ctx, const cgpu_lb6_key *key, cgpu_lb6_service *va
 int cgpu_lb6_get_next_key(cgpu_ctx *ctx, const cgpu_lb6_key *key, cgpu_lb6_key *next_out);
 size_t cgpu_lb6_count(cgpu_ctx *ctx);
 
+/* ------------------------------------------------------------------ */
+/* reverse NAT maps cilium_lb4_reverse_nat / cilium_lb6_reverse_nat     */
+/* (bpf/lib/lb.h:54-68; the agent fills them for every service,         */
+/* daemon/loadbalancer.go:345-350, pkg/maps/lbmap/lbmap.go:229-260)      */
+/* ------------------------------------------------------------------ */
+#pragma pack(push, 1)
+/* struct lb4_reverse_nat, bpf/lib/common.h:441-444 (packed, 6 B): the
+ * service's address and port, network order */
+typedef struct cgpu_lb4_reverse_nat {
+	uint32_t address;
+	uint16_t port;
+} cgpu_lb4_reverse_nat;
+/* struct lb6_reverse_nat, bpf/lib/common.h:422-425 (packed, 18 B) */
+typedef struct cgpu_lb6_reverse_nat {
+	uint8_t address[16];
+	uint16_t port;
+} cgpu_lb6_reverse_nat;
+#pragma pack(pop)
+
+/* Semantics of the cgpu_lb4_* calls (CGPU_ANY / NOEXIST / EXIST, -ENOENT,
+ * -E2BIG at lb_max_entries per map: both are CILIUM_LB_MAP_MAX_ENTRIES in the
+ * reference).  `index` is the __u16 key as the datapath holds it: the same
+ * 16 raw bits as cgpu_lb4_service.rev_nat_index and cgpu_ct_entry.
+ * rev_nat_index (lb.h:570 looks ct_state->rev_nat_index up as stored).
+ * get_next_key (NULL = first) walks the indices in ascending raw order.  The
+ * calls work on a host-only context; the maps always exist (there is no
+ * switch) and reach the device at cgpu_commit as dense tables, built only
+ * for a non-empty map.  Only the cgpu_classify_*_rnat calls read them. */
+int cgpu_revnat4_update(cgpu_ctx *ctx, uint16_t index, const cgpu_lb4_reverse_nat *val, uint64_t flags);
+int cgpu_revnat4_delete(cgpu_ctx *ctx, uint16_t index);
+int cgpu_revnat4_lookup(cgpu_ctx *ctx, uint16_t index, cgpu_lb4_reverse_nat *val_out);
+int cgpu_revnat4_get_next_key(cgpu_ctx *ctx, const uint16_t *index, uint16_t *next_out);
+size_t cgpu_revnat4_count(cgpu_ctx *ctx);
+int cgpu_revnat6_update(cgpu_ctx *ctx, uint16_t index, const cgpu_lb6_reverse_nat *val, uint64_t flags);
+int cgpu_revnat6_delete(cgpu_ctx *ctx, uint16_t index);
+int cgpu_revnat6_lookup(cgpu_ctx *ctx, uint16_t index, cgpu_lb6_reverse_nat *val_out);
+int cgpu_revnat6_get_next_key(cgpu_ctx *ctx, const uint16_t *index, uint16_t *next_out);
+size_t cgpu_revnat6_count(cgpu_ctx *ctx);
+
 /* The flow hash the batch entry points use when no hash column is given
  * (skb->hash comes from the kernel's flow dissector, which the reference
  * does not contain: SURVEY §8c).  Over the stored (network-order) fields. */
@@ -924,8 +963,9 @@ typedef struct cgpu_ctlb_out {
  *   allowed CT_NEW creates its entry with the service's rev_nat_index,
  *   slave and lb_loopback, the address entry of ct_create4 (tuple->daddr :=
  *   backend or IPV4_LOOPBACK; conntrack.h:697-725) and the ICMP entry.
- *   A hit entry's reverse NAT goes through the empty cilium_lb4_reverse_nat
- *   map (a no-op, lb.h:562-576).  Ingress packets are as cgpu_classify_v4_ct.
+ *   A hit entry's reverse NAT changes the frame only (lb.h:562-576): no
+ *   output of this call depends on it; cgpu_classify_v4_ctlb_rnat reports
+ *   it.  Ingress packets are as cgpu_classify_v4_ct.
  * hash: skb->hash per packet (NULL: cgpu_flow_hash over the 5-tuple).
  * Service drops: verdict -158, ct_ret CGPU_CT_NONE, identity 0, stage 6,
  * metrics reason 158 egress.  Ordering, streams and the capacity caveat as
@@ -984,8 +1024,9 @@ typedef struct cgpu_tuples_v6_ct {
  * ct_create6 (:588-639, with its ICMPv6 related entry) of an allowed CT_NEW
  * packet.  An ingress entry is created with rev_nat_index =
  * daddr.s6_addr32[3] & 0xFFFF (bpf_lxc.c:748); a hit entry's reverse NAT
- * goes through the empty cilium_lb6_reverse_nat map (a no-op, lib/lb.h:
- * 305-317).  Outputs, ordering and the capacity caveat as cgpu_classify_v4_ct.
+ * (lib/lb.h:305-317) changes the frame only: no output of this call depends
+ * on it; cgpu_classify_v6_ct_rnat reports it.  Outputs, ordering and the
+ * capacity caveat as cgpu_classify_v4_ct.
  */
 int cgpu_classify_v6_ct(cgpu_ctx *ctx, const cgpu_tuples_v6_ct *t, size_t n, uint32_t now,
 			int32_t *verdict, uint8_t *ct_ret, uint32_t *identity, uint8_t *stage,
@@ -1027,13 +1068,68 @@ int cgpu_classify_v6_ctlb(cgpu_ctx *ctx, const cgpu_tuples_v6_ct *t, const uint3
 			  uint32_t now, const cgpu_ctlb6_out *out, void *stream);
 
 /* ------------------------------------------------------------------ */
+/* reverse NAT of service replies on the conntrack paths                */
+/* ------------------------------------------------------------------ */
+/*
+ * The frame's source (IPv4: and destination) fields as the endpoint program
+ * leaves them, per packet (device pointers, each may be NULL).  They start
+ * as the input, on the _ctlb paths as the service step left them (daddr :=
+ * the backend; IPv4 saddr := IPV4_LOOPBACK when the backend is the sender,
+ * lb.h:761-766), and change where the program calls lb4_rev_nat / lb6_rev_nat
+ * with the ct_state of the entry the packet hit:
+ *   IPv4 egress  (bpf_lxc.c:531-541): ct_ret REPLY or RELATED, rev_nat_index != 0
+ *   IPv4 ingress (bpf_lxc.c:909-918): ct_ret REPLY only, rev_nat_index != 0,
+ *                                     !lb_loopback (REV_NAT_F_TUPLE_SADDR: the
+ *                                     same frame result)
+ *   IPv6 egress  (bpf_lxc.c:222-235): ct_ret REPLY or RELATED, rev_nat_index != 0
+ *   IPv6 ingress (bpf_lxc.c:778-785): any hit (ESTABLISHED too) whose entry has
+ *                                     rev_nat_index != 0; a CT_NEW packet never
+ * The index is looked up as stored (lb.h:570 / :312); a miss changes nothing
+ * (applied 0).  A hit (applied 1) is __lb4_rev_nat (lb.h:485-550) /
+ * __lb6_rev_nat (:254-294): when nat->port != 0 the source port of a TCP or
+ * UDP frame := nat->port (reverse_map_l4_port, :218-252; ICMP keeps its port
+ * word; its DROP_UNKNOWN_L4 is unreachable behind ct_lookup's protocol gate);
+ * IPv4 with the entry's lb_loopback: daddr := the old saddr; saddr :=
+ * nat->address.  Verdicts, ct_ret, identities, counters, metrics and both
+ * maps do not depend on this step.  Checksums are not modelled.
+ */
+typedef struct cgpu_rnat4_out {
+	uint32_t *saddr, *daddr; /* network order */
+	uint16_t *sport;
+	uint8_t *applied;        /* 1: the map held the index and __lb4_rev_nat ran */
+} cgpu_rnat4_out;
+typedef struct cgpu_rnat6_out {
+	uint8_t *saddr;          /* [n][16], 16-byte aligned */
+	uint16_t *sport;
+	uint8_t *applied;
+} cgpu_rnat6_out;
+
+/* The calls they extend, with that output; rn == NULL: exactly those calls
+ * (their kernels).  With rn the conntrack walks run instantiations that also
+ * store the hit entry's rev_nat_index | lb_loopback << 16 per packet, and a
+ * rewrite pass follows the finish.  -ENODEV on a host-only context. */
+int cgpu_classify_v4_ct_rnat(cgpu_ctx *ctx, const cgpu_tuples_v4_ct *t, size_t n, uint32_t now,
+			     int32_t *verdict, uint8_t *ct_ret, uint32_t *identity, uint8_t *stage,
+			     const cgpu_rnat4_out *rn, void *stream);
+int cgpu_classify_v4_ctlb_rnat(cgpu_ctx *ctx, const cgpu_tuples_v4_ct *t, const uint32_t *hash, size_t n,
+			       uint32_t now, const cgpu_ctlb_out *out, const cgpu_rnat4_out *rn,
+			       void *stream);
+int cgpu_classify_v6_ct_rnat(cgpu_ctx *ctx, const cgpu_tuples_v6_ct *t, size_t n, uint32_t now,
+			     int32_t *verdict, uint8_t *ct_ret, uint32_t *identity, uint8_t *stage,
+			     const cgpu_rnat6_out *rn, void *stream);
+int cgpu_classify_v6_ctlb_rnat(cgpu_ctx *ctx, const cgpu_tuples_v6_ct *t, const uint32_t *hash, size_t n,
+			       uint32_t now, const cgpu_ctlb6_out *out, const cgpu_rnat6_out *rn,
+			       void *stream);
+
+/* ------------------------------------------------------------------ */
 /* checkpoint / resume                                      */
 /* ------------------------------------------------------------------ */
 /* The host mirror is authoritative (the device is rebuilt from it at any
  * commit), so a checkpoint is the mirror written to a file: every ipcache,
  * policy (with each entry's packets / bytes counters), prefilter CIDR,
- * endpoint, lb4 / lb6 and lxc entry, the PreFilter revision, and both
- * conntrack maps.  The reference's counterpart is its maps pinned in bpffs
+ * endpoint, lb4 / lb6 and lxc entry, the PreFilter revision, both
+ * conntrack maps and both reverse-NAT maps (a file written before those two
+ * sections existed restores with them empty).  The reference's counterpart is its maps pinned in bpffs
  * plus the ipcache replay into listeners (pkg/ipcache/ipcache.go:328-338).
  * save: atomic (written to path.tmp, then renamed).  restore: into a context
  * whose maps are all empty (else -EEXIST); the file is validated whole
