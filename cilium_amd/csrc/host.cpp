@@ -1910,8 +1910,25 @@ struct BuildState {
  * kernels.hip).  A host shadow serves the bpf(2)-style map calls; the device
  * copy is authoritative once a batch ran (dev_newer) and is refreshed from
  * the shadow before the next batch after host edits (host_newer). */
-/* LRU mode's bloom filter of a batch's conntrack keys: 2^22 words (2^27 bits) */
-#define CT_BLOOM_WORDS (1u << 22)
+/* LRU mode's filter of a batch's conntrack keys (one hash, one bit per key):
+ * sized per call to about 16 bits per key the batch marks, a power of two of
+ * words.  The floor of 2^12 words keeps small batches' filters sparse at the
+ * cost of a 16-KiB clear.  The cap is 2^26 words (256 MiB): by the device's
+ * nominal store rate (not measured here) its clear is of the order of
+ * 0.1 ms, about 1 % of the ~10 ms a batch of the 32M packets that fill it
+ * takes, and the single
+ * 32-bit hash (bit index = hash, word = hash >> 5) addresses 2^27 words at
+ * most, so a larger filter would add clear time and nearly no selectivity.
+ * Past the cap the filter densifies and a create may find no victim within
+ * CT_EVICT_SCAN slots (cgpu_ct_lru_stats counts those). */
+#define CT_BLOOM_MIN_LOG2 12u
+#define CT_BLOOM_MAX_LOG2 26u
+/* keys marked per packet: reply, forward and ICMP tuple on the plain paths;
+ * on the service paths the service and ICMP key, per candidate slave (two)
+ * five tuple keys and the address entry, two more ICMP keys, and the
+ * record's three or four again */
+#define CT_MARKS_PLAIN 3u
+#define CT_MARKS_SVC 20u
 
 struct CtMap {
 	bool v6 = false;
@@ -1926,6 +1943,7 @@ struct CtMap {
 	uint4 *d_keys2 = nullptr, *d_vals2 = nullptr;
 	uint32_t *d_gc = nullptr;
 	uint32_t *d_bloom = nullptr; /* LRU mode: the batch's key filter */
+	uint32_t bloom_cap = 0;      /* ... its allocation in words (grow-only) */
 	uint64_t compactions = 0;
 	uint32_t sw() const { return v6 ? 4u : 1u; } /* uint4 key words per slot */
 };
@@ -6038,7 +6056,9 @@ static int ct_push(CtMap &m)
 	if (!m.d_keys) {
 		HIP_OR_EIO(hipMalloc((void **)&m.d_keys, m.keys.size() * 16));
 		HIP_OR_EIO(hipMalloc((void **)&m.d_vals, m.vals.size() * 16));
-		HIP_OR_EIO(hipMalloc((void **)&m.d_count, 8));
+		/* {live, tombstones}, then LRU mode's 64-bit {evictions, no victim} */
+		HIP_OR_EIO(hipMalloc((void **)&m.d_count, 24));
+		HIP_OR_EIO(hipMemset(m.d_count, 0, 24));
 		m.host_newer = true;
 	}
 	if (!m.host_newer)
@@ -6312,6 +6332,33 @@ CGPU_EXPORT int cgpu_ct4_gc(cgpu_ctx *c, uint32_t time, uint64_t *deleted_out)
 	return ct_gc_l(c, c->ct4, time, deleted_out);
 }
 
+/* the filter's size in words for `keys` marked keys (see CT_BLOOM_MIN_LOG2);
+ * exported as a test hook, not part of cgpu.h */
+CGPU_EXPORT uint32_t cgpu__ct_lru_filter_words(uint64_t keys)
+{
+	uint32_t lg = CT_BLOOM_MIN_LOG2;
+	/* 16 bits per key = keys / 2 words */
+	while (lg < CT_BLOOM_MAX_LOG2 && ((uint64_t)1 << lg) < (keys + 1) / 2)
+		lg++;
+	return 1u << lg;
+}
+
+CGPU_EXPORT int cgpu_ct_lru_stats(cgpu_ctx *c, int v6, uint64_t out[2])
+{
+	if (!c || !out)
+		return fail(-EINVAL, "null argument");
+	CtMap &m = v6 ? c->ct6 : c->ct4;
+	std::lock_guard<std::mutex> g(c->mu);
+	out[0] = out[1] = 0;
+	if (c->device >= 0 && m.d_count) {
+		/* counted by the walkers behind the live / tombstone words */
+		HIP_OR_EIO(hipSetDevice(c->device));
+		HIP_OR_EIO(hipMemcpyAsync(out, m.d_count + 2, 16, hipMemcpyDeviceToHost, c->ct_stream));
+		HIP_OR_EIO(hipStreamSynchronize(c->ct_stream));
+	}
+	return 0;
+}
+
 CGPU_EXPORT int cgpu_ct_stats(cgpu_ctx *c, int v6, uint64_t *out)
 {
 	if (!c || !out)
@@ -6473,13 +6520,19 @@ static int ct_classify(cgpu_ctx *c, const cgpu_snapshot &s, uint64_t *delta, CtM
 	const uint32_t headroom = m.max > live ? m.max - live : 0u;
 	const uint32_t chunk = std::min<uint32_t>(256u, std::max<uint32_t>(1u, headroom / 32768u));
 	ct_table T{m.d_keys, m.d_vals, m.mask, m.max, m.d_count, chunk};
-	/* LRU mode (the plain paths; the service paths keep failing creates
-	 * closed): the batch's key filter, 16 MiB */
-	if (c->cfg.ct_lru && !svc) {
-		if (!m.d_bloom)
-			HIP_OR_EIO(hipMalloc((void **)&m.d_bloom, (size_t)CT_BLOOM_WORDS * 4u));
+	/* LRU mode: the batch's key filter, sized for this call, grow-only */
+	if (c->cfg.ct_lru) {
+		const uint32_t words = cgpu__ct_lru_filter_words(a.n * (svc ? CT_MARKS_SVC : CT_MARKS_PLAIN));
+		if (words > m.bloom_cap) {
+			HIP_OR_EIO(hipStreamSynchronize(cs));
+			(void)hipFree(m.d_bloom);
+			m.d_bloom = nullptr;
+			m.bloom_cap = 0;
+			HIP_OR_EIO(hipMalloc((void **)&m.d_bloom, (size_t)words * 4u));
+			m.bloom_cap = words;
+		}
 		T.bloom = m.d_bloom;
-		T.bloom_mask = CT_BLOOM_WORDS - 1u;
+		T.bloom_mask = words - 1u;
 		T.lru = 1;
 	}
 	a.delta = delta;

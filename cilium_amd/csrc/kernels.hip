@@ -4791,6 +4791,23 @@ struct CtK6S : CtK6 {
 	static constexpr bool SVC = true;
 };
 
+/* A slot whose tag a prober compares the key of: LIVE, and HOLD, the claim
+ * an eviction holds while it judges a slot's key a second time (ct_evict;
+ * LRU mode only).  The slot may have been recycled by a create of this batch
+ * since the eviction first judged it, and its owner -- the only lane that
+ * probes for that key -- must not pass over it while the hold lasts (lanes
+ * of one wave run their divergent paths one after the other, so it can last
+ * long).  Under HOLD the key words are whole: the slot was LIVE, published
+ * after its key stores had drained, and the eviction turns HOLD into CLAIM
+ * before it clears a word.  A CLAIM slot (an insert writing its key, a delete
+ * or an eviction clearing it) is never compared: its key words may be torn
+ * ({daddr, saddr} stored, the ports word not yet, which is a whole key of
+ * the same pair with ports 0). */
+__device__ __forceinline__ bool ct_tag_holds(uint32_t tag)
+{
+	return tag == CT_TAG_LIVE || tag == CT_TAG_HOLD;
+}
+
 /* Probe for k (low 16 bits of the meta word = nexthdr | flags << 8).
  * Returns the slot or -1; *free_at = the first tombstone on the chain, else
  * the empty slot that ended it (where an insert of k may start). */
@@ -4824,7 +4841,7 @@ __device__ __forceinline__ int ct_find(const ct_table &T, const typename K::key 
 			}
 			K::reload(T, h, s);
 		}
-		if (tag == CT_TAG_LIVE && K::same(s, k))
+		if (ct_tag_holds(tag) && K::same(s, k))
 			return (int)h;
 		if (tag == CT_TAG_TOMB && ff == 0xFFFFFFFFu)
 			ff = h;
@@ -4847,6 +4864,7 @@ struct ct_acct {
 	int *res;   /* LDS: reserved, unused capacity */
 	int *live;  /* LDS: live entries removed (deletes), to return */
 	int *tombs; /* LDS: tombstone delta */
+	int *lru;   /* LDS: LRU mode's [0] evictions, [1] creates that found no victim */
 };
 
 __device__ __forceinline__ bool ct_take(const ct_table &T, const ct_acct &A)
@@ -4922,7 +4940,43 @@ template <class K> __device__ __forceinline__ void ct_mark(uint32_t *bloom, uint
 /* evict one live entry outside the batch's filter: its capacity passes to
  * the caller's create (the live count does not change), the slot becomes a
  * tombstone as a delete leaves it (claimed first, so no prober compares
- * and no insert reuses it while its words are cleared) */
+ * and no insert reuses it while its words are cleared).
+ *
+ * The tag word's low half is only nexthdr | flags << 8, so the CAS of the
+ * LIVE tag word does not prove that the slot still holds the key that was
+ * judged: between the key reload and the CAS another evictor may have
+ * tombstoned the slot and a create of this batch reused it (CLAIM, key
+ * words, LIVE) with the same low half (ABA).  So the CAS takes the slot to
+ * HOLD, not CLAIM, and the key is read and judged again under the hold:
+ *   - Under HOLD nobody writes the key words (inserts CAS from EMPTY / TOMB,
+ *     evictions from LIVE); whoever made the slot LIVE drained its key
+ *     stores (vmcnt 0) before publishing the tag, so the agent-scope reload
+ *     returns the whole key the slot stands for.  The slot's owner, if it is
+ *     a key of the batch, keeps finding it: probers compare the key of a
+ *     HOLD slot (ct_tag_holds).
+ *   - The owner may DELETE the entry by slot meanwhile: ct_erase exchanges
+ *     its own claim word (CLAIM, low half 0) over the hold.  The tag is
+ *     therefore read again AFTER the key words have arrived (vmcnt 0 between
+ *     them): if it still is this lane's hold word, the delete had not begun
+ *     when the key was read, so the key judged is whole.
+ *   - If that key is outside the filter it is no key of the batch, whether
+ *     it is the key judged before the CAS or one a recycling put there since
+ *     (the filter does not change during a walk), so no lane of the batch
+ *     can delete or probe for it; the hold becomes CLAIM by a CAS from this
+ *     lane's hold word -- which fails if a delete took the slot after all --
+ *     and only then the words are cleared and the slot turns TOMB.
+ *   - If it is in the filter, the slot was recycled by this batch: nothing
+ *     was cleared, the LIVE tag word goes back by a CAS from the hold word
+ *     (failing, harmlessly, under a delete), and the scan goes on.
+ * This narrows the window, it does not close it: the hold word (HOLD | the
+ * protocol and flags) is not unique to a lane.  If, between this lane's key
+ * reload and its tag re-read, the owner deletes the slot, an insert reuses
+ * it with the same low half AND another eviction takes it to HOLD, the tag
+ * reads as this lane's hold over a key read torn, and its CAS to CLAIM
+ * takes the other lane's hold.  That is a whole delete, insert and hold
+ * between two adjacent loads of one lane.  Exactness needs a generation or
+ * lane id in the tag word, whose 16 bits the states and the compare of the
+ * low half use up. */
 template <class K> __device__ __forceinline__ bool ct_evict(const ct_table &T, const ct_acct &A, uint32_t start)
 {
 	uint32_t h = start & T.mask;
@@ -4935,14 +4989,26 @@ template <class K> __device__ __forceinline__ bool ct_evict(const ct_table &T, c
 		K::meta(s) = tw;
 		if (ct_in_batch<K>(T, s))
 			continue;
-		if (atomicCAS(K::tagp(T, h), tw, (CT_TAG_CLAIM << 16) | (tw & 0xFFFFu)) != tw)
+		const uint32_t hw = (CT_TAG_HOLD << 16) | (tw & 0xFFFFu);
+		if (atomicCAS(K::tagp(T, h), tw, hw) != tw)
+			continue;
+		K::reload(T, h, s);
+		__builtin_amdgcn_s_waitcnt(0); /* the key words, then the tag */
+		__atomic_signal_fence(__ATOMIC_SEQ_CST);
+		const bool held = __hip_atomic_load(K::tagp(T, h), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == hw;
+		const bool mine = held && !ct_in_batch<K>(T, s);
+		/* one CAS from this lane's hold word for both outcomes */
+		const uint32_t next = mine ? (CT_TAG_CLAIM << 16) | (tw & 0xFFFFu) : tw;
+		if (atomicCAS(K::tagp(T, h), hw, next) != hw || !mine)
 			continue;
 		K::clear(T, h);
 		__builtin_amdgcn_s_waitcnt(0);
 		__hip_atomic_exchange(K::tagp(T, h), CT_TAG_TOMB << 16, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 		atomicAdd(A.tombs, 1);
+		atomicAdd(A.lru, 1);
 		return true;
 	}
+	atomicAdd(A.lru + 1, 1);
 	return false;
 }
 
@@ -5123,14 +5189,49 @@ template <> struct ct_rec<CtK6> {
 /* ct_create4's address entry (conntrack.h:697-725) of forward tuple k for
  * the egress direction: daddr := state->addr; on loopback flags :=
  * TUPLE_F_IN and saddr := state->svc_addr */
-__device__ __forceinline__ uint4 ct_addr_key(uint4 k, const ct_pkt &q)
+__device__ __forceinline__ uint4 ct_addr_key(uint4 k, uint32_t addr, uint32_t svc_addr, bool loopback)
 {
-	k.x = q.addr;
-	if (q.lbf & LBF_LOOPBACK) {
+	k.x = addr;
+	if (loopback) {
 		k.w = (k.w & ~0xFF00u) | (TUPLE_F_IN << 8);
-		k.y = q.svc_addr;
+		k.y = svc_addr;
 	}
 	return k;
+}
+__device__ __forceinline__ uint4 ct_addr_key(uint4 k, const ct_pkt &q)
+{
+	return ct_addr_key(k, q.addr, q.svc_addr, q.lbf & LBF_LOOPBACK);
+}
+
+/* What lb4_local's outcome so (svc_out: SVC_XLATED | LBS_* << 8 | slave << 16,
+ * the target, the dport rewrite) makes of an egress packet {sa, da, dp}:
+ * xd / dp the frame's daddr / dport as lb4_xlate left them, da tuple.daddr
+ * (the service address is kept on loopback, lb.h:769-770), addr / svc_addr
+ * the ct_state ct_create4 stores (loopback source NAT: lb.h:753-767).  The
+ * service prep derives its records from it, and LRU mode's k_svc_mark the
+ * keys a candidate backend would give (one derivation for both). */
+struct svc_xl4 {
+	uint32_t da, dp, xd, addr, svc_addr;
+	bool lb;
+};
+__device__ __forceinline__ svc_xl4 svc_xlate4(const cgpu_snapshot &s, const uint4 &so, uint32_t sa, uint32_t da,
+					      uint32_t dp)
+{
+	const uint32_t lbs = (so.x >> 8) & 3u, tg = so.y;
+	svc_xl4 x;
+	x.lb = lbs != 0;
+	x.xd = tg;
+	x.da = x.lb ? da : tg; /* tuple->daddr = svc->target */
+	x.dp = (so.z & 0xFFFFu) ? so.z & 0xFFFFu : dp; /* lb4_xlate's port rewrite */
+	x.addr = (lbs & LBS_SNAT) ? s.ipv4_loopback : tg;
+	x.svc_addr = (lbs & LBS_SNAT) ? sa : 0u;
+	return x;
+}
+/* ... and of an IPv6 one (svc_out[2i], the target in svc_out[2i + 1] becomes
+ * tuple.daddr, lb.h:475): the dport as lb6_xlate left it */
+__device__ __forceinline__ uint32_t svc_xlate6_dport(const uint4 &so, uint32_t dp)
+{
+	return (so.y & 0xFFFFu) ? so.y & 0xFFFFu : dp;
 }
 
 /*   IPv6 behind the service step: the IPv6 record with {sec, cst, rev_nat,
@@ -5242,15 +5343,13 @@ __device__ __forceinline__ bool prep4_pre(const cgpu_snapshot &s, const ct_args 
 			return false;
 		}
 		if ((so.x & 3u) == SVC_XLATED) {
-			const uint32_t lbs = (so.x >> 8) & 3u, tg = so.y;
-			const bool lb = lbs != 0;
-			xd = tg;
-			if (!lb)
-				da = tg; /* tuple->daddr = svc->target */
-			if (so.z & 0xFFFFu)
-				dp = so.z & 0xFFFFu; /* lb4_xlate's port rewrite */
-			addr = (lbs & LBS_SNAT) ? s.ipv4_loopback : tg;
-			saddr2 = (lbs & LBS_SNAT) ? sa : 0u;
+			const svc_xl4 x = svc_xlate4(s, so, sa, da, dp);
+			const bool lb = x.lb;
+			xd = x.xd;
+			da = x.da;
+			dp = x.dp;
+			addr = x.addr;
+			saddr2 = x.svc_addr;
 			/* the address entry's pair {addr, loopback ? svc_addr : daddr}
 			 * against the packet's own {saddr, daddr} */
 			const uint32_t b = lb ? saddr2 : da;
@@ -5268,6 +5367,7 @@ __device__ __forceinline__ bool prep4_pre(const cgpu_snapshot &s, const ct_args 
 	}
 	if (pr == 1u) {
 		const uint32_t type = w & 0xFFu;
+		/* (this tuple setup is restated by ct_tuple_z for LRU mode's marks) */
 		if (type == 3u || type == 11u || type == 12u) /* DEST_UNREACH, TIME_EXCEEDED, PARAMETERPROB */
 			tfl |= TUPLE_F_RELATED;
 		else if (type == 0u) /* ECHOREPLY: tuple->dport = ICMP_ECHO */
@@ -5475,7 +5575,7 @@ __global__ __launch_bounds__(256) void k_ct_prep_q(cgpu_snapshot s, ct_args a, t
 			tfl[u] = eg[u] ? TUPLE_F_IN : 0u;
 			meta[u] = eg[u] ? CTM_EGRESS : 0u;
 			z[u] = 0;
-			if (pr[u] == 1u) { /* as k_ct_prep */
+			if (pr[u] == 1u) { /* as k_ct_prep; also restated by ct_tuple_z (LRU marks) */
 				const uint32_t type = w[u] & 0xFFu;
 				if (type == 3u || type == 11u || type == 12u)
 					tfl[u] |= TUPLE_F_RELATED;
@@ -5575,8 +5675,8 @@ __global__ __launch_bounds__(256) void k_ct_prep6_q(cgpu_snapshot s, ct_args a, 
 					const uint4 so = a.svc_out[2u * j];
 					drop[u] = (so.x & 3u) == SVC_DROP;
 					xl[u] = (so.x & 3u) == SVC_XLATED;
-					if (xl[u] && (so.y & 0xFFFFu))
-						dp = so.y & 0xFFFFu; /* lb6_xlate's port rewrite */
+					if (xl[u])
+						dp = svc_xlate6_dport(so, dp);
 				}
 			}
 			dpx[u] = dp;
@@ -5589,7 +5689,7 @@ __global__ __launch_bounds__(256) void k_ct_prep6_q(cgpu_snapshot s, ct_args a, 
 			tfl[u] = eg[u] ? TUPLE_F_IN : 0u;
 			meta[u] = eg[u] ? CTM_EGRESS : 0u;
 			z[u] = 0;
-			if (pr[u] == 58u) { /* as k_ct_prep6 */
+			if (pr[u] == 58u) { /* as k_ct_prep6; also restated by ct_tuple_z (LRU marks) */
 				const uint32_t type = w[u] & 0xFFu;
 				if (type >= 1u && type <= 4u)
 					tfl[u] |= TUPLE_F_RELATED;
@@ -5962,8 +6062,7 @@ __global__ __launch_bounds__(256) void k_ct_prep6(cgpu_snapshot s, ct_args a, tu
 			}
 			if ((so.x & 3u) == SVC_XLATED) {
 				da = a.svc_out[2u * i + 1u]; /* tuple->daddr = svc->target (lb.h:475) */
-				if (so.y & 0xFFFFu)
-					dp = so.y & 0xFFFFu; /* lb6_xlate's port rewrite */
+				dp = svc_xlate6_dport(so, dp);
 				rev = so.y >> 16;
 				svcw = (so.x >> 16) | ((((so.x >> 8) & LBS_ENTRY) ? LBF_LOOPBACK : 0u) << 16);
 			}
@@ -6244,7 +6343,7 @@ __device__ __forceinline__ void ct_chain_eval(const ct_table &T, const typename 
 		}
 		K::reload(T, ch.h, s);
 	}
-	if (tag == CT_TAG_LIVE && K::same(s, k)) {
+	if (ct_tag_holds(tag) && K::same(s, k)) {
 		ch.slot = (int)ch.h;
 		return;
 	}
@@ -6666,6 +6765,18 @@ __global__ __launch_bounds__(256) void k_gather_u32(const uint32_t *src, const u
 /* One service packet of a group: lb4_local (lb.h:700-775) against the map.
  * k = the CT_SERVICE tuple; no forward lookup for CT_SERVICE (conntrack.h:
  * 553-558). */
+/* lb4_local's outcome (svc_out) for backend row b of `slave`: loopback
+ * source NAT when the sender is the backend, lb4_xlate's port rewrite */
+__device__ __forceinline__ uint4 svc_res4(const cgpu_snapshot &s, uint32_t lbs, uint32_t slave, const uint4 &b,
+					  uint32_t sa, uint32_t kd, uint32_t pr)
+{
+	if (sa == b.x)
+		lbs |= LBS_SNAT;
+	const uint32_t port = b.y & 0xFFFFu;
+	const uint32_t rw = ((s.lb_flags & CGPU_LB_L4) && port && kd != port && (pr == 6u || pr == 17u)) ? port : 0u;
+	return make_uint4(SVC_XLATED | (lbs << 8) | (slave << 16), b.x, rw | ((b.z & 0xFFFFu) << 16), 0u);
+}
+
 __device__ __forceinline__ uint4 ct_svc_step(const cgpu_snapshot &s, const ct_table &T, const ct_acct &A,
 					     ct_cache<CtK4> &c, const ct_srec &r, uint32_t now)
 {
@@ -6714,11 +6825,7 @@ __device__ __forceinline__ uint4 ct_svc_step(const cgpu_snapshot &s, const ct_ta
 			ctc_put(c, ci, ctc_pos(c, ci), e);
 		}
 	}
-	if (r.r0.y == b.x)
-		lbs |= LBS_SNAT;
-	const uint32_t port = b.y & 0xFFFFu;
-	const uint32_t rw = ((s.lb_flags & CGPU_LB_L4) && port && kd != port && (pr == 6u || pr == 17u)) ? port : 0u;
-	return make_uint4(SVC_XLATED | (lbs << 8) | (slave << 16), b.x, rw | ((b.z & 0xFFFFu) << 16), 0u);
+	return svc_res4(s, lbs, slave, b, r.r0.y, kd, pr);
 }
 
 /* The IPv6 service step: lb6_local with CONNTRACK (lb.h:426-483) over
@@ -6809,6 +6916,15 @@ __global__ __launch_bounds__(256) void k_svc_prep6(cgpu_snapshot s, ct_args a)
 	}
 }
 
+/* lb6_local's outcome (svc_out[2i]) for backend row val of `slave` */
+__device__ __forceinline__ uint4 svc_res6(const cgpu_snapshot &s, uint32_t lbs, uint32_t slave, const uint4 &val,
+					  uint32_t kd, uint32_t pr)
+{
+	const uint32_t port = val.x & 0xFFFFu;
+	const uint32_t rw = ((s.lb_flags & CGPU_LB_L4) && port && kd != port && (pr == 6u || pr == 17u)) ? port : 0u;
+	return make_uint4(SVC_XLATED | (lbs << 8) | (slave << 16), rw | ((val.y & 0xFFFFu) << 16), 0u, 0u);
+}
+
 __device__ __forceinline__ uint4 ct_svc_step6(const cgpu_snapshot &s, const ct_table &T, const ct_acct &A,
 					      ct_cache<CtK6> &c, const ct_srec6 &r, uint32_t now, uint4 &tg)
 {
@@ -6855,17 +6971,31 @@ __device__ __forceinline__ uint4 ct_svc_step6(const cgpu_snapshot &s, const ct_t
 			ctc_put(c, ci, ctc_pos(c, ci), e);
 		}
 	}
-	const uint32_t port = val.x & 0xFFFFu;
-	const uint32_t rw = ((s.lb_flags & CGPU_LB_L4) && port && kd != port && (pr == 6u || pr == 17u)) ? port : 0u;
-	return make_uint4(SVC_XLATED | (lbs << 8) | (slave << 16), rw | ((val.y & 0xFFFFu) << 16), 0u, 0u);
+	return svc_res6(s, lbs, slave, val, kd, pr);
 }
 
 #ifndef CT_RETB
 #define CT_RETB 16 /* results a walker lane buffers before storing them */
 #endif
 
+/* LRU mode: a tuple's keys into the batch's filter.  k = the reply-direction
+ * tuple (a record's key): ct_lookup's two lookups and the ICMP entry a create
+ * of the forward tuple writes; `both`: the ICMP key of either direction */
+template <class K>
+__device__ __forceinline__ void ct_mark_tuple(uint32_t *bloom, uint32_t mask, const typename K::key &k, bool both)
+{
+	const typename K::key fk = K::reversed(k);
+	ct_mark<K>(bloom, mask, k);
+	ct_mark<K>(bloom, mask, fk);
+	ct_mark<K>(bloom, mask, K::related(fk));
+	if (both)
+		ct_mark<K>(bloom, mask, K::related(k));
+}
+
 /* LRU mode: the keys packet i's conntrack step can look up or create (the
- * reply tuple, the forward tuple, its ICMP tuple) into the batch's filter */
+ * reply tuple, the forward tuple, its ICMP tuple; behind the IPv4 service
+ * step the address entry of its create, inline or owed to phase 2) into the
+ * batch's filter */
 template <class K> __global__ __launch_bounds__(256) void k_ct_mark(ct_args a, uint32_t *bloom, uint32_t mask)
 {
 	for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < a.n; i += (uint64_t)gridDim.x * 256u) {
@@ -6873,10 +7003,276 @@ template <class K> __global__ __launch_bounds__(256) void k_ct_mark(ct_args a, u
 		if (r.meta() & CTM_GATED)
 			continue;
 		const typename K::key k = r.key();
-		const typename K::key fk = K::reversed(k);
-		ct_mark<K>(bloom, mask, k);
-		ct_mark<K>(bloom, mask, fk);
-		ct_mark<K>(bloom, mask, K::related(fk));
+		ct_mark_tuple<K>(bloom, mask, k, false);
+		if constexpr (K::ADDR) {
+			const ct_pkt q = r.pkt();
+			if (q.addr)
+				ct_mark<K>(bloom, mask, ct_addr_key(K::reversed(k), q));
+		}
+	}
+}
+
+/* ct_lookup4 / ct_lookup6's tuple of a packet from its columns: the RELATED
+ * flag into tfl, z = the reply-direction ports word.  false: a protocol the
+ * conntrack step gates.
+ * A SECOND COPY of what the preps compute inline together with their meta
+ * bits (prep4_pre, k_ct_prep_q, k_ct_prep6, k_ct_prep6_q, and the service
+ * preps k_svc_prep / k_svc_prep6 for the CT_SERVICE tuple): LRU mode's mark
+ * kernels must build exactly the keys the walks touch, so a change to the
+ * ICMP type classes or the ports word there has to be made here too (each
+ * copy carries a pointer to this one).  The LRU tests compare every packet
+ * against the restatement under eviction, which is what catches a drift. */
+template <bool V6>
+__device__ __forceinline__ bool ct_tuple_z(uint32_t pr, uint32_t w, uint32_t sp, uint32_t dp, uint32_t &tfl,
+					    uint32_t &z)
+{
+	z = 0;
+	if (pr == (V6 ? 58u : 1u)) {
+		const uint32_t type = w & 0xFFu;
+		const uint32_t echo = V6 ? 128u : 8u, reply = V6 ? 129u : 0u;
+		if (V6 ? (type >= 1u && type <= 4u) : (type == 3u || type == 11u || type == 12u))
+			tfl |= TUPLE_F_RELATED;
+		else if (type == reply)
+			z = echo;
+		else if (type == echo)
+			z = echo << 16;
+		return true;
+	}
+	if (pr == 6u || pr == 17u) {
+		z = sp | (dp << 16);
+		return true;
+	}
+	return false;
+}
+
+/* ---- LRU mode on the service paths: the batch's keys BEFORE the service walk ----
+ * The service walk creates CT_SERVICE entries (and may evict for them) before
+ * the translated tuples exist, so the filter cannot be filled from the
+ * conntrack prep's records.  It is filled with a superset instead, computed
+ * from the packet columns, the service records (k_svc_prep) and read-only
+ * probes of the map as the batch found it:
+ *   every service packet: its CT_SERVICE key k and related(k);
+ *   every other packet: the keys of its untranslated tuple (as k_ct_mark);
+ *   every service packet, for each slave it can end up with: the keys of the
+ *   tuple that backend translates it to -- reply, forward, both ICMP keys
+ *   and (IPv4) the address entry ct_create4 writes -- derived by the same
+ *   functions the service step and the service prep use (svc_res4 /
+ *   svc_xlate4, svc_res6 / svc_xlate6_dport).
+ * The candidate slaves of a packet with hash h:
+ *   (a) h % master count + 1 (lb4_select_slave / lb6_select_slave);
+ *   (b) the slave its entry k holds in the map as the batch found it (with
+ *       the entry's lb_loopback); an ICMP error's k is the pair's ICMP entry;
+ *   (c) for each of (a) and (b) that the backend lookup misses, the
+ *       re-selection h % count' + 1 (lb.h:737-744 / :462-469), deterministic
+ *       from the tables: the row lb4_lookup_service returned (where the
+ *       re-selecting packet goes) and the new slave (what the entry's next
+ *       reader looks up), followed as a chain (svc_mark_cand4);
+ *   (d) for (a), the backend an ICMP error of the pair gets for that slave
+ *       through ITS frontend (key.dport 0, the L3 service): ICMP keys only.
+ * Why this covers every key the batch touches.  The tables do not change
+ * during a batch and k is marked, so the entry k is either the map's for
+ * the whole batch or created in it.  The slave a packet P reads or sets is
+ *   - the one the map held for k: P's own (b);
+ *   - one P sets: creating k, its (a); re-selecting after a miss, its (c).
+ *     A re-selecting packet is sent to the row lb4_lookup_service returned
+ *     for the MISSED slave -- a function of the tables and that slave, not
+ *     of any hash -- and stores the new slave;
+ *   - one a packet W of the batch wrote: W's (a) or (c).  If k is a
+ *     connection's key, W has P's saddr, ports and protocol (they are k's),
+ *     so whatever a slave gives P it gives W: W marked the tuple of the row
+ *     its slave finds, and, where that lookup misses, the tuple of the row
+ *     the re-selection is sent to (the same for P, whatever P's hash: a
+ *     generator may redraw a packet's hash, only the missed slave matters)
+ *     and, for the slave W stored in turn, the row it finds or the row its
+ *     own miss is sent to (svc_mark_cand4);
+ *   - for an ICMP error, whose k is the ICMP entry related(k) every
+ *     connection of {saddr, service address} shares: the slave of whichever
+ *     connection created it, i.e. that creator's (a) -- ct_update_slave
+ *     rewrites only k, never the ICMP entry.  The error's tuple is then the
+ *     ICMP tuple of {saddr, that backend}, read in both directions: the
+ *     creator marked both ICMP keys of its (a) backend, and (d) the ones its
+ *     slave gives through the error's own frontend.  Where that frontend has
+ *     no row for the slave, the error has no tuple: its key.dport is 0, so
+ *     lb4_lookup_service asks the same L3 frontend for the same slave again,
+ *     misses again and the packet is dropped (DROP_NO_SERVICE).
+ * Not covered (a superset of the issue's candidates, not of every
+ * conceivable batch): within ONE batch, a connection whose stored slave is
+ * re-selected, whose re-selected slave has no backend row either, whose
+ * next packet carries another hash than the first (so stores another slave
+ * than this chain followed) and whose third packet reads that one.  Each
+ * step needs a slave freshly drawn from a count that includes a row that
+ * is gone.  Such a packet's translated keys are marked only by the second
+ * pass, after the service walk; an entry under one of them that the
+ * service walk evicted makes it a CT_NEW where the map held a connection.
+ * Loopback: lb_loopback of an entry created in the batch is clear, of the
+ * map's entry it is (b)'s; the source NAT case (saddr == backend) follows
+ * from the candidate row itself.  After the service prep the actual records
+ * are marked on top (k_ct_mark over the S key classes, filter not cleared),
+ * so the conntrack walk's own evictions do not lean on this argument: it is
+ * the service walk's evictions that do. */
+struct svc_mark_args {
+	uint32_t *bloom;
+	uint32_t mask;
+};
+
+/* the slave and lb_loopback entry k holds in the map (read-only, before the
+ * walks: plain loads) */
+template <class K>
+__device__ __forceinline__ bool svc_stored(const ct_table &T, const typename K::key &k, uint32_t &slave, uint32_t &lbs)
+{
+	uint32_t fa, pend = 0;
+	const int slot = ct_find<K>(T, k, &fa, pend);
+	if (slot < 0)
+		return false;
+	const uint4 c = T.vals[4u * (uint32_t)slot + 2u];
+	slave = c.z & 0xFFFFu;
+	lbs = (c.y & CTB_LB_LOOPBACK) ? LBS_ENTRY : 0u;
+	return true;
+}
+
+/* one IPv4 packet's columns */
+struct mark_pkt4 {
+	uint32_t sa, da, sp, dp, pr, w;
+};
+
+/* the keys of the tuple lb4_local's outcome so gives service packet p */
+__device__ __forceinline__ void svc_mark_xl4(const cgpu_snapshot &s, const svc_mark_args &m, const mark_pkt4 &p,
+					     const uint4 &so)
+{
+	const svc_xl4 x = svc_xlate4(s, so, p.sa, p.da, p.dp);
+	uint32_t tfl = TUPLE_F_IN, z;
+	if (!ct_tuple_z<false>(p.pr, p.w, p.sp, x.dp, tfl, z))
+		return;
+	const uint4 k = uint4{x.da, p.sa, z, p.pr | (tfl << 8)};
+	ct_mark_tuple<CtK4>(m.bloom, m.mask, k, true);
+	if (x.addr)
+		ct_mark<CtK4>(m.bloom, m.mask, ct_addr_key(CtK4::reversed(k), x.addr, x.svc_addr, x.lb));
+}
+
+/* candidate `slave` of service packet p (record r): lb4_lookup_slave, on a
+ * miss the re-selection, as ct_svc_step.  A re-selecting packet is sent to
+ * the row lb4_lookup_service returned while the entry keeps the NEW slave,
+ * so the entry's next reader looks that one up: one more step, which marks
+ * the new slave's row or, if that misses too, the row the reader's own
+ * re-selection is sent to (a function of the missed slave, not of a hash).
+ * A third step would look up h % count + 1 again: the same slave whenever
+ * the count is the same */
+#define SVC_MARK_CHAIN 2
+__device__ __forceinline__ void svc_mark_cand4(const cgpu_snapshot &s, const svc_mark_args &m, const mark_pkt4 &p,
+					       const ct_srec &r, uint32_t slave, uint32_t lbs)
+{
+	for (int step = 0; step < SVC_MARK_CHAIN; step++) {
+		uint32_t kd = r.r1.w & 0xFFFFu;
+		uint4 f = uint4{r.r0.x, kd | (r.r1.w & 0xFFFF0000u), r.r2.x, r.r2.y}, b;
+		const bool hit = lb_row(s.lb, f, slave, &b);
+		if (!hit) {
+			uint32_t probes = 0;
+			if (!lb_service(s, r.r0.x, &kd, slave, &b, &f, &probes) || !(b.y >> 16))
+				return; /* DROP_NO_SERVICE: no translated tuple, the entry keeps its slave */
+			slave = r.r1.z % (b.y >> 16) + 1u;
+		}
+		svc_mark_xl4(s, m, p, svc_res4(s, lbs, slave, b, p.sa, kd, p.pr));
+		if (hit)
+			return;
+	}
+}
+
+__global__ __launch_bounds__(256) void k_svc_mark(cgpu_snapshot s, ct_table T, ct_args a, svc_mark_args m)
+{
+	const uint64_t stride = (uint64_t)gridDim.x * 256u;
+	for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < a.n; i += stride) {
+		const mark_pkt4 p{a.saddr[i], a.daddr[i], a.sport[i], a.dport[i], a.proto[i], a.l4[i]};
+		if (!a.f2[i]) { /* not a service packet: its untranslated tuple */
+			uint32_t tfl = (a.flags[i] & 1u) ? TUPLE_F_IN : 0u, z;
+			if (ct_tuple_z<false>(p.pr, p.w, p.sp, p.dp, tfl, z))
+				ct_mark_tuple<CtK4>(m.bloom, m.mask, uint4{p.da, p.sa, z, p.pr | (tfl << 8)}, false);
+			continue;
+		}
+		const ct_srec r = ct_srec::load(a.rec, (uint32_t)i, false);
+		const uint4 k = uint4{r.r0.x, r.r0.y, r.r0.z, r.r0.w & 0xFFFFu};
+		ct_mark<CtK4>(m.bloom, m.mask, k);
+		ct_mark<CtK4>(m.bloom, m.mask, CtK4::related(k));
+		const uint32_t mc = r.r1.w >> 16;
+		const uint32_t sa_ = mc ? r.r1.z % mc + 1u : 0u; /* (a) */
+		svc_mark_cand4(s, m, p, r, sa_, 0u);
+		uint32_t sb, lb;
+		if (svc_stored<CtK4>(T, k, sb, lb)) /* (b) */
+			svc_mark_cand4(s, m, p, r, sb, lb);
+		if (!((k.w >> 8) & TUPLE_F_RELATED) && (s.lb_flags & CGPU_LB_L3)) {
+			/* (d): the pair's ICMP errors read slave (a) from related(k) and
+			 * look it up under the L3 service of the address */
+			uint4 b;
+			if (lb_row(s.lb, lb_frontend(s.lb, r.r0.x, 0u), sa_, &b)) {
+				const svc_xl4 x = svc_xlate4(s, svc_res4(s, 0u, sa_, b, p.sa, 0u, 1u), p.sa, p.da, 0u);
+				const uint4 ki = uint4{x.da, p.sa, 0u, 1u | ((TUPLE_F_IN | TUPLE_F_RELATED) << 8)};
+				ct_mark<CtK4>(m.bloom, m.mask, ki);
+				ct_mark<CtK4>(m.bloom, m.mask, CtK4::reversed(ki));
+			}
+		}
+	}
+}
+
+/* candidate `slave` of IPv6 service packet (record r): lb6_lookup_slave, on
+ * a miss the re-selection, as ct_svc_step6 (the chain as svc_mark_cand4);
+ * then the translated tuple's keys */
+__device__ __forceinline__ void svc_mark_cand6(const cgpu_snapshot &s, const svc_mark_args &m, const ct_srec6 &r,
+					       uint32_t sp, uint32_t w, uint32_t slave, uint32_t lbs)
+{
+	/* w: the packet's L4 word from its column (the service record keeps it
+	 * for TCP only, and the ICMPv6 type decides the translated tuple) */
+	const uint32_t pr = r.r2.y & 0xFFu, f = r.r3.z;
+	for (int step = 0; step < SVC_MARK_CHAIN; step++) {
+		uint32_t kd = r.r3.y & 0xFFFFu;
+		uint4 tg, val;
+		const bool hit = lb6_get<true>(s.lb6, r.r0, f, kd, slave, tg, val);
+		if (!hit) {
+			if (!lb6_service(s, r.r0, f, &kd, slave, tg, val) || !(val.x >> 16))
+				return; /* DROP_NO_SERVICE: no translated tuple, the entry keeps its slave */
+			slave = r.r3.x % (val.x >> 16) + 1u;
+		}
+		const uint32_t dp = svc_xlate6_dport(svc_res6(s, lbs, slave, val, kd, pr), r.r3.w);
+		uint32_t tfl = TUPLE_F_IN, z;
+		if (!ct_tuple_z<true>(pr, w, sp, dp, tfl, z))
+			return;
+		ct_mark_tuple<CtK6>(m.bloom, m.mask, CtK6::key{tg, r.r1, z, pr | (tfl << 8)}, true);
+		if (hit)
+			return;
+	}
+}
+
+__global__ __launch_bounds__(256) void k_svc_mark6(cgpu_snapshot s, ct_table T, ct_args a, svc_mark_args m)
+{
+	const uint64_t stride = (uint64_t)gridDim.x * 256u;
+	const uint4 *sa16 = reinterpret_cast<const uint4 *>(a.saddr);
+	const uint4 *da16 = reinterpret_cast<const uint4 *>(a.daddr);
+	for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < a.n; i += stride) {
+		const uint32_t sp = a.sport[i], pr = a.proto[i];
+		if (!a.f2[i]) { /* not a service packet: its untranslated tuple */
+			uint32_t tfl = (a.flags[i] & 1u) ? TUPLE_F_IN : 0u, z;
+			if (ct_tuple_z<true>(pr, a.l4[i], sp, a.dport[i], tfl, z))
+				ct_mark_tuple<CtK6>(m.bloom, m.mask,
+						    CtK6::key{ld_x4<true>(da16 + i), ld_x4<true>(sa16 + i), z, pr | (tfl << 8)},
+						    false);
+			continue;
+		}
+		const ct_srec6 r = ct_srec6::load(a.rec, (uint32_t)i, false);
+		const CtK6::key k{r.r0, r.r1, r.r2.x, r.r2.y & 0xFFFFu};
+		ct_mark<CtK6>(m.bloom, m.mask, k);
+		ct_mark<CtK6>(m.bloom, m.mask, CtK6::related(k));
+		const uint32_t mc = r.r3.y >> 16;
+		const uint32_t sa_ = mc ? r.r3.x % mc + 1u : 0u; /* (a) */
+		svc_mark_cand6(s, m, r, sp, a.l4[i], sa_, 0u);
+		uint32_t sb, lb;
+		if (svc_stored<CtK6>(T, k, sb, lb)) /* (b) */
+			svc_mark_cand6(s, m, r, sp, a.l4[i], sb, lb);
+		if (!((k.m >> 8) & TUPLE_F_RELATED) && (s.lb_flags & CGPU_LB_L3)) { /* (d) */
+			uint4 tg, val;
+			if (lb6_get<true>(s.lb6, r.r0, r.r3.z, 0u, sa_, tg, val)) {
+				const CtK6::key ki{tg, r.r1, 0u, 58u | ((TUPLE_F_IN | TUPLE_F_RELATED) << 8)};
+				ct_mark<CtK6>(m.bloom, m.mask, ki);
+				ct_mark<CtK6>(m.bloom, m.mask, CtK6::reversed(ki));
+			}
+		}
 	}
 }
 
@@ -6913,9 +7309,16 @@ extern "C" __attribute__((visibility("default"))) int cgpu_diag_walk_clock(unsig
 }
 #endif
 
-template <class K, int MODE, bool RN = false>
-__global__ __launch_bounds__(256, K::ADDR ? CGPU_WALK_MINB_SVC : CGPU_WALK_W) void k_ct_walk(cgpu_snapshot s, ct_table T, ct_args a)
+/* LRU: the instantiation that can evict (cgpu_config.ct_lru).  The map
+ * functions read T.lru; without LRU it is the constant 0 here, so the default
+ * mode's walkers hold no eviction, no claim-first publication and no LRU
+ * counters at all.  With LRU the flag stays a run-time value (see
+ * launch_ct_walk for the one default-mode walker that runs this form) */
+template <class K, int MODE, bool RN = false, bool LRU = false>
+__global__ __launch_bounds__(256, K::ADDR ? CGPU_WALK_MINB_SVC : CGPU_WALK_W) void k_ct_walk(cgpu_snapshot s, ct_table T_, ct_args a)
 {
+	ct_table T = T_;
+	T.lru = LRU ? T_.lru : 0u;
 #ifdef CGPU_DIAG_WALK_CLOCK
 	const unsigned long long dg_t0 = __builtin_amdgcn_s_memrealtime();
 	uint32_t dg_steps = 0;
@@ -6923,7 +7326,7 @@ __global__ __launch_bounds__(256, K::ADDR ? CGPU_WALK_MINB_SVC : CGPU_WALK_W) vo
 	using R = std::conditional_t<MODE == WALK_SVC, std::conditional_t<K::V6 != 0, ct_srec6, ct_srec>,
 				     ct_rec<K>>;
 	constexpr bool DFLT = MODE == WALK_PKT && ct_dflt<K>::ON;
-	__shared__ int s_acct[3];
+	__shared__ int s_acct[5];
 	/* each lane's last CT_RETB results (packet index, ct result), stored
 	 * together: a scattered 1-byte store is a memory-side write whose
 	 * completion every later load wait of the lane also waits for (vmcnt
@@ -6949,10 +7352,10 @@ __global__ __launch_bounds__(256, K::ADDR ? CGPU_WALK_MINB_SVC : CGPU_WALK_W) vo
 		}
 		nret = 0;
 	};
-	if (threadIdx.x < 3)
+	if (threadIdx.x < 5)
 		s_acct[threadIdx.x] = 0;
 	__syncthreads();
-	const ct_acct A{&s_acct[0], &s_acct[1], &s_acct[2]};
+	const ct_acct A{&s_acct[0], &s_acct[1], &s_acct[2], &s_acct[3]};
 	const uint32_t nh = *a.n_heads;
 	const uint32_t stride = gridDim.x * 256u;
 #if CTC == 4
@@ -7094,6 +7497,13 @@ __global__ __launch_bounds__(256, K::ADDR ? CGPU_WALK_MINB_SVC : CGPU_WALK_W) vo
 			atomicSub(&T.count[0], (uint32_t)back);
 		if (s_acct[2])
 			atomicAdd(&T.count[1], (uint32_t)s_acct[2]);
+		if (LRU && T.lru) { /* cgpu_ct_lru_stats: two 64-bit totals behind the counts */
+			unsigned long long *lt = reinterpret_cast<unsigned long long *>(T.count + 2);
+			if (s_acct[3])
+				atomicAdd(lt, (unsigned long long)s_acct[3]);
+			if (s_acct[4])
+				atomicAdd(lt + 1, (unsigned long long)s_acct[4]);
+		}
 	}
 }
 
@@ -7709,10 +8119,22 @@ template <class K> static hipError_t launch_ct_finish(const cgpu_snapshot &s, co
 template <class K, int MODE>
 static void launch_ct_walk(const cgpu_snapshot &s, const ct_table &T, const ct_args &a, hipStream_t st)
 {
-	if (a.rn)
+	/* phase 1 of the IPv4 service path also runs the evicting form in the
+	 * default mode (the eviction behind the run-time flag, as before this
+	 * form existed): at its 168-VGPR budget the form without it spills 31
+	 * VGPRs instead of 21 and measured 6 % slower on the whole ctlb step
+	 *  */
+	constexpr bool keep = K::ADDR && MODE == WALK_PKT;
+	if (T.lru || (keep && !a.rn)) {
+		if (a.rn)
+			hipLaunchKernelGGL((k_ct_walk<K, MODE, true, true>), dim3(CT_WALK_GRID), dim3(256), 0, st, s, T, a);
+		else
+			hipLaunchKernelGGL((k_ct_walk<K, MODE, false, true>), dim3(CT_WALK_GRID), dim3(256), 0, st, s, T, a);
+	} else if (a.rn) {
 		hipLaunchKernelGGL((k_ct_walk<K, MODE, true>), dim3(CT_WALK_GRID), dim3(256), 0, st, s, T, a);
-	else
+	} else {
 		hipLaunchKernelGGL((k_ct_walk<K, MODE>), dim3(CT_WALK_GRID), dim3(256), 0, st, s, T, a);
+	}
 }
 
 /* Reverse NAT of the replies (cgpu_classify_v{4,6}_ct{,lb}_rnat), after the
@@ -7835,6 +8257,34 @@ static hipError_t ct_phase2(const cgpu_snapshot &s, const ct_table &T, const ct_
 	return hipGetLastError();
 }
 
+/* LRU mode: the batch's key filter, cleared once per call ... */
+static hipError_t ct_filter_clear(const ct_table &T, hipStream_t st)
+{
+	return hipMemsetAsync(const_cast<uint32_t *>(T.bloom), 0, ((size_t)T.bloom_mask + 1u) * 4u, st);
+}
+/* ... the keys of the conntrack prep's records into it ... */
+template <class K> static void launch_ct_mark(const ct_table &T, const ct_args &a, hipStream_t st)
+{
+	const unsigned g = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((a.n + 255) / 256, 8192));
+	hipLaunchKernelGGL(k_ct_mark<K>, dim3(g), dim3(256), 0, st, a, const_cast<uint32_t *>(T.bloom), T.bloom_mask);
+}
+/* ... and, on the service paths before the service walk, the superset of the
+ * keys the batch can touch (k_svc_mark / k_svc_mark6, after k_svc_prep{,6}) */
+template <class K>
+static hipError_t launch_svc_mark(const cgpu_snapshot &s, const ct_table &T, const ct_args &a, hipStream_t st)
+{
+	hipError_t e = ct_filter_clear(T, st);
+	if (e != hipSuccess)
+		return e;
+	const unsigned g = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((a.n + 255) / 256, 8192));
+	const svc_mark_args m{const_cast<uint32_t *>(T.bloom), T.bloom_mask};
+	if (K::V6)
+		hipLaunchKernelGGL(k_svc_mark6, dim3(g), dim3(256), 0, st, s, T, a, m);
+	else
+		hipLaunchKernelGGL(k_svc_mark, dim3(g), dim3(256), 0, st, s, T, a, m);
+	return hipGetLastError();
+}
+
 template <class K>
 static hipError_t launch_ct(const cgpu_snapshot &s, const ct_table &T, const ct_launch &L, hipStream_t st)
 {
@@ -7882,11 +8332,10 @@ static hipError_t launch_ct(const cgpu_snapshot &s, const ct_table &T, const ct_
 	if (T.lru) {
 		/* LRU mode: every key the batch can touch into the filter the
 		 * evictions avoid (the prep's records are complete) */
-		hipError_t e0 = hipMemsetAsync(const_cast<uint32_t *>(T.bloom), 0, ((size_t)T.bloom_mask + 1u) * 4u, st);
+		hipError_t e0 = ct_filter_clear(T, st);
 		if (e0 != hipSuccess)
 			return e0;
-		hipLaunchKernelGGL(k_ct_mark<K>, dim3(g), dim3(256), 0, st, a, const_cast<uint32_t *>(T.bloom),
-				   T.bloom_mask);
+		launch_ct_mark<K>(T, a, st);
 	}
 	uint32_t nh;
 	hipError_t e = ct_group_sort(s, L, a, L.n, &nh, st, K::V6 != 0);
@@ -7934,7 +8383,10 @@ static hipError_t ct_svc_walk(const cgpu_snapshot &s, const ct_table &T, const c
 	uint32_t nh;
 	if ((e = ct_group_sort(s, L, a, m, &nh, st, K::V6 != 0)) != hipSuccess)
 		return e;
-	hipLaunchKernelGGL((k_ct_walk<K, WALK_SVC>), dim3(CT_WALK_GRID), dim3(256), 0, st, s, T, a);
+	if (T.lru)
+		hipLaunchKernelGGL((k_ct_walk<K, WALK_SVC, false, true>), dim3(CT_WALK_GRID), dim3(256), 0, st, s, T, a);
+	else
+		hipLaunchKernelGGL((k_ct_walk<K, WALK_SVC>), dim3(CT_WALK_GRID), dim3(256), 0, st, s, T, a);
 	return hipGetLastError();
 }
 
@@ -7949,7 +8401,10 @@ hipError_t launch_classify_v6_ctlb(const cgpu_snapshot &s, const ct_table &T, co
 	const unsigned g = (unsigned)std::min<uint64_t>((L.n + 255) / 256, 8192);
 	hipLaunchKernelGGL(k_svc_prep6, dim3(g), dim3(256), 0, st, s, a);
 	uint32_t nh;
-	hipError_t e = ct_svc_walk<CtK6>(s, T, L, a, st);
+	hipError_t e;
+	if (T.lru && (e = launch_svc_mark<CtK6>(s, T, a, st)) != hipSuccess)
+		return e;
+	e = ct_svc_walk<CtK6>(s, T, L, a, st);
 	if (e != hipSuccess)
 		return e;
 	if (CGPU_CT_SVC_PRE6 && s.cluster_id && s.cluster_id <= DIR_PAYLOAD_MASK && !CGPU_CT_SVC_DECQ6) {
@@ -7970,6 +8425,8 @@ hipError_t launch_classify_v6_ctlb(const cgpu_snapshot &s, const ct_table &T, co
 		hipLaunchKernelGGL(k_ct_prep6<true>, dim3(g), dim3(256), 0, st, s, a, tun_args{});
 		launch_ct_decq<CtK6S>(s, a, st);
 	}
+	if (T.lru) /* the actual records on top of the superset */
+		launch_ct_mark<CtK6S>(T, a, st);
 	e = ct_group_sort(s, L, a, L.n, &nh, st, true);
 	if (e != hipSuccess)
 		return e;
@@ -8008,7 +8465,10 @@ hipError_t launch_classify_v4_ctlb(const cgpu_snapshot &s, const ct_table &T, co
 	const unsigned g = (unsigned)std::min<uint64_t>((L.n + 255) / 256, 8192);
 	hipLaunchKernelGGL(k_svc_prep, dim3(g), dim3(256), 0, st, s, a);
 	uint32_t nh;
-	hipError_t e = ct_svc_walk<CtK4>(s, T, L, a, st);
+	hipError_t e;
+	if (T.lru && (e = launch_svc_mark<CtK4>(s, T, a, st)) != hipSuccess)
+		return e;
+	e = ct_svc_walk<CtK4>(s, T, L, a, st);
 	if (e != hipSuccess)
 		return e;
 	e = hipMemsetAsync(a.ctl, 0, 16, st);
@@ -8031,6 +8491,8 @@ hipError_t launch_classify_v4_ctlb(const cgpu_snapshot &s, const ct_table &T, co
 		hipLaunchKernelGGL((k_ct_prep<true, true>), dim3(g), dim3(256), 0, st, s, a);
 	}
 	launch_ct_decq<CtK4S>(s, a, st);
+	if (T.lru) /* the actual records (after the serial re-prep) on top of the superset */
+		launch_ct_mark<CtK4S>(T, a, st);
 	e = ct_group_sort(s, L, a, L.n, &nh, st);
 	if (e != hipSuccess)
 		return e;

@@ -511,7 +511,8 @@ typedef struct ipc_tun {
  * keys[slot] (16 B, one gather per probe) = the 14-byte struct ipv4_ct_tuple
  * (bpf/lib/common.h:359-366) plus a 16-bit slot tag in the top half of .w:
  *   .x daddr  .y saddr  .z dport | sport << 16  .w nexthdr | flags << 8 | tag << 16
- *   tag 0 empty, CT_TAG_LIVE occupied, CT_TAG_CLAIM being written, CT_TAG_TOMB
+ *   tag 0 empty, CT_TAG_LIVE occupied, CT_TAG_CLAIM being written (CT_TAG_HOLD:
+ *   held whole by an eviction, kernels.hip ct_evict), CT_TAG_TOMB
  *   deleted (probe chains run through it; inserts reuse it).
  * vals[slot] (64 B = 4 x uint4, one row per slot) = struct ct_entry
  * (common.h:380-408, 56 B) in its own byte layout, then 8 spare bytes.
@@ -519,6 +520,7 @@ typedef struct ipc_tun {
  * inserts, updates and deletes entries in place. */
 #define CT_TAG_EMPTY 0u
 #define CT_TAG_LIVE 1u
+#define CT_TAG_HOLD 0xFFFDu /* LRU mode: an eviction judging the (whole) key again */
 #define CT_TAG_CLAIM 0xFFFEu
 #define CT_TAG_TOMB 0xFFFFu
 

@@ -348,6 +348,12 @@ class Engine:
         check(self.L.cgpu_ct_stats(self.h, int(v6), out.ctypes.data_as(C.c_void_p)), "cgpu_ct_stats")
         return {"live": int(out[0]), "tombstones": int(out[1]), "compactions": int(out[2])}
 
+    def ct_lru_stats(self, v6: bool = False) -> dict:
+        """cgpu_ct_lru_stats: LRU mode's evictions and creates that found no victim."""
+        out = np.zeros(2, np.uint64)
+        check(self.L.cgpu_ct_lru_stats(self.h, int(v6), out.ctypes.data_as(C.c_void_p)), "cgpu_ct_lru_stats")
+        return {"evictions": int(out[0]), "no_victim": int(out[1])}
+
     def ct4_flush(self) -> None:
         check(self.L.cgpu_ct4_flush(self.h), "cgpu_ct4_flush")
 

@@ -170,13 +170,24 @@ typedef struct cgpu_config {
 	/* 1: the conntrack maps behave as BPF_MAP_TYPE_LRU_HASH, which the
 	 * reference builds CT_MAP4 / CT_MAP6 as on every kernel with LRU maps
 	 * (bpf/bpf_lxc.c:53-75, probe bpf/probes/raw_lru_map.t): a create that
-	 * finds the map full evicts an entry instead of failing.  The victim is
-	 * the engine's own choice, not the kernel's per-CPU LRU list: a live
-	 * entry none of the batch's packets can look up or create (a key filter
-	 * built before the walk; the scan covers CT_EVICT_SCAN = 4096 slots from
-	 * a hashed start), so every packet of a batch gets the result the map it
-	 * started from gives it.  cgpu_classify_v{4,6}_ct only: the service paths
-	 * keep failing the create (DROP_NO_SERVICE / DROP_CT_CREATE_FAILED).
+	 * finds the map full evicts an entry instead of failing.  All four
+	 * conntrack calls, cgpu_classify_v{4,6}_ct and cgpu_classify_v{4,6}_ctlb
+	 * (the service walk's CT_SERVICE creates included), and their _tun /
+	 * _rnat forms.
+	 * The victim is the engine's own choice, not the kernel's per-CPU LRU
+	 * list: before any walk of a batch, every key a packet of the batch can
+	 * look up or create is marked in a filter (on the service paths a
+	 * superset, from every backend a service packet can be sent to); a create
+	 * that finds the map full scans CT_EVICT_SCAN = 4096 slots from a hashed
+	 * start and evicts the first live entry whose key is outside the filter.
+	 * So every packet of a batch gets the result the map the batch found
+	 * gives it, and no key the batch touches is evicted; across batches an
+	 * entry idle in one batch may be gone in the next.
+	 * The one remaining failure: a create still fails (DROP_CT_CREATE_FAILED,
+	 * on the service step DROP_NO_SERVICE) when no entry outside the batch's
+	 * keys lies within those 4096 slots, which is the case when one batch
+	 * needs more entries than the map holds (or marks so many keys that the
+	 * filter, capped at 256 MiB, saturates).  cgpu_ct_lru_stats counts both.
 	 * 0 (default): the non-LRU build, CT_MAP_SIZE enforced as -E2BIG. */
 	uint32_t ct_lru;
 	/* 1: cgpu_commit also compiles the second word of every ipcache value,
@@ -861,6 +872,11 @@ int cgpu_ct4_flush(cgpu_ctx *ctx);
  * that finds more than a quarter of the slots tombstones first re-inserts the
  * live entries into a clean table, on the device).  v6: cilium_ct6_global. */
 int cgpu_ct_stats(cgpu_ctx *ctx, int v6, uint64_t *out);
+/* (new, diagnostic) LRU mode's totals of the map since the context was
+ * created, after everything queued on it: out[0] evictions, out[1] creates
+ * that found no victim (and failed).  Zeros without ct_lru.  -EINVAL on a
+ * NULL argument. */
+int cgpu_ct_lru_stats(cgpu_ctx *ctx, int v6, uint64_t out[2]);
 
 /* A batch of IPv4 packets for the stateful path (device pointers). */
 typedef struct cgpu_tuples_v4_ct {
