@@ -346,6 +346,12 @@ static inline uint8_t *oh_get(const struct ohash *h, const void *key)
 /* ====================================================================== */
 #define N_METRICS (256 * 4 * 2)
 
+/* struct lb4_reverse_nat / lb6_reverse_nat (bpf/lib/common.h) and whether
+ * the index is in the map; both maps are BPF_MAP_TYPE_HASH keyed by the raw
+ * __u16 (lb.h:44-58), restated as dense arrays */
+struct or_rn4 { uint32_t address; uint16_t port, present; };
+struct or_rn6 { uint8_t address[16]; uint16_t port, present; };
+
 struct or_ctx {
 	or_config cfg;
 	struct lpm_trie ipcache;  /* ipcache_key data = {pad[3], family, ip[16]} */
@@ -356,6 +362,8 @@ struct or_ctx {
 	struct ohash lxc;           /* endpoint_key -> present */
 	struct ohash lb;            /* lb4_key (8 B) -> lb4_service (12 B) */
 	struct ohash lb6;           /* lb6_key (20 B) -> lb6_service (24 B) */
+	struct or_rn4 *rn4;         /* cilium_lb4_reverse_nat: [65536] by raw index */
+	struct or_rn6 *rn6;         /* cilium_lb6_reverse_nat */
 	uint8_t *lxcinfo;           /* [n_lxcinfo][32] per-endpoint identity */
 	size_t n_lxcinfo;
 	struct ohash ct;            /* ipv4_ct_tuple (14 B) -> ct_entry (56 B) */
@@ -433,6 +441,8 @@ or_ctx *or_create(void)
 	oh_init(&c->lb6, 20, 24);
 	oh_init(&c->ct, 14, 56);
 	oh_init(&c->ct6, 38, 56);
+	c->rn4 = calloc(65536, sizeof(*c->rn4));
+	c->rn6 = calloc(65536, sizeof(*c->rn6));
 	c->ct_max = 1000000; /* ctmap.go:101 MapNumEntriesGlobal */
 	c->ct6_max = 1000000;
 	return c;
@@ -458,6 +468,8 @@ void or_destroy(or_ctx *c)
 		oh_destroy(&c->policy[i]);
 	free(c->policy);
 	free(c->lxcinfo);
+	free(c->rn4);
+	free(c->rn6);
 	free(c);
 }
 
@@ -2198,8 +2210,12 @@ static inline int ct_alive(const struct ct_val *e)
 
 /* __ct_lookup, conntrack.h:198-259, on the raw key of either map: 1 =
  * found (entry updated), 0 = miss */
-static int ct_lookup_kb(struct ohash *m, const uint8_t *kb, int action, int dir, int tcp,
-			uint16_t w, uint32_t len, uint32_t now)
+/* what __ct_lookup copies from the entry it hit into ct_state
+ * (conntrack.h:213-217); untouched on a miss */
+struct ct_hit { uint16_t rev_nat; uint8_t loopback; };
+
+static inline int ct_lookup_hit(struct ohash *m, const uint8_t *kb, int action, int dir, int tcp,
+				uint16_t w, uint32_t len, uint32_t now, struct ct_hit *hit)
 {
 	uint8_t *p;
 	struct ct_val e;
@@ -2207,6 +2223,10 @@ static int ct_lookup_kb(struct ohash *m, const uint8_t *kb, int action, int dir,
 	if (!p)
 		return 0;
 	memcpy(&e, p, 56);
+	if (hit) {
+		hit->rev_nat = e.rev_nat_index;
+		hit->loopback = (e.bits & 8u) ? 1 : 0; /* lb_loopback */
+	}
 	if (ct_alive(&e))
 		ct_timeout(&e, now, tcp, dir, w);
 	if (dir == CT_INGRESS) { /* CONNTRACK_ACCOUNTING */
@@ -2230,12 +2250,143 @@ static int ct_lookup_kb(struct ohash *m, const uint8_t *kb, int action, int dir,
 	return 1;
 }
 
+static int ct_lookup_kb(struct ohash *m, const uint8_t *kb, int action, int dir, int tcp,
+			uint16_t w, uint32_t len, uint32_t now)
+{
+	return ct_lookup_hit(m, kb, action, dir, tcp, w, len, now, NULL);
+}
+
 static int ct_lookup_one(or_ctx *c, const struct ct_key *k, int action, int dir, int tcp,
-			 uint16_t w, uint32_t len, uint32_t now)
+			 uint16_t w, uint32_t len, uint32_t now, struct ct_hit *hit)
 {
 	uint8_t kb[14];
 	ct_key_bytes(k, kb);
-	return ct_lookup_kb(&c->ct, kb, action, dir, tcp, w, len, now);
+	return ct_lookup_hit(&c->ct, kb, action, dir, tcp, w, len, now, hit);
+}
+
+/* ---------------------------------------------------------------------- */
+/* Reverse NAT of service replies: cilium_lb{4,6}_reverse_nat and           */
+/* lb4_rev_nat / lb6_rev_nat at their call sites in bpf_lxc.c               */
+/* ---------------------------------------------------------------------- */
+int or_revnat4_update(or_ctx *c, uint16_t index, const void *val6)
+{
+	struct or_rn4 *r = &c->rn4[index];
+	memcpy(&r->address, val6, 4);
+	memcpy(&r->port, (const uint8_t *)val6 + 4, 2);
+	r->present = 1;
+	return 0;
+}
+
+int or_revnat4_delete(or_ctx *c, uint16_t index)
+{
+	if (!c->rn4[index].present)
+		return -ENOENT;
+	memset(&c->rn4[index], 0, sizeof(c->rn4[index]));
+	return 0;
+}
+
+int or_revnat6_update(or_ctx *c, uint16_t index, const void *val18)
+{
+	struct or_rn6 *r = &c->rn6[index];
+	memcpy(r->address, val18, 16);
+	memcpy(&r->port, (const uint8_t *)val18 + 16, 2);
+	r->present = 1;
+	return 0;
+}
+
+int or_revnat6_delete(or_ctx *c, uint16_t index)
+{
+	if (!c->rn6[index].present)
+		return -ENOENT;
+	memset(&c->rn6[index], 0, sizeof(c->rn6[index]));
+	return 0;
+}
+
+/* the frame fields the reverse NAT can change */
+struct rn_frame4 { uint32_t saddr, daddr; uint16_t sport; uint8_t applied; };
+
+/* lb4_rev_nat (lb.h:562-576) + __lb4_rev_nat (:485-550) on the frame, with
+ * the ct_state of the entry ct_lookup4 hit.  Both values of
+ * REV_NAT_F_TUPLE_SADDR give the same frame: old_sip is the frame's saddr
+ * (the tuple's saddr is the frame's at the ingress call site). */
+static void rn4_rev_nat(const or_ctx *c, const struct ct_hit *st, uint8_t nexthdr, struct rn_frame4 *f)
+{
+	const struct or_rn4 *nat = &c->rn4[st->rev_nat];
+	uint32_t old_sip;
+	if (!nat->present)
+		return; /* nat == NULL: return 0 */
+	/* reverse_map_l4_port (lb.h:218-252): TCP / UDP only, ICMP breaks */
+	if (nat->port && (nexthdr == PROTO_TCP || nexthdr == PROTO_UDP))
+		f->sport = nat->port;
+	old_sip = f->saddr;
+	if (st->loopback)
+		f->daddr = old_sip;
+	f->saddr = nat->address;
+	f->applied = 1;
+}
+
+/* the endpoint program's two call sites: egress bpf_lxc.c:531-541 (case
+ * CT_RELATED / CT_REPLY: if (ct_state.rev_nat_index)), ingress :909-918
+ * (ret == CT_REPLY && rev_nat_index && !loopback) */
+static void rn4_site(const or_ctx *c, int egress, int ret, const struct ct_hit *st, uint8_t nexthdr,
+		     struct rn_frame4 *f)
+{
+	if (egress) {
+		if ((ret == 2 || ret == 3) && st->rev_nat)
+			rn4_rev_nat(c, st, nexthdr, f);
+	} else if (ret == 2 && st->rev_nat && !st->loopback) {
+		rn4_rev_nat(c, st, nexthdr, f);
+	}
+}
+
+static void rn4_store(const or_rnat4_out *rn, size_t i, const struct rn_frame4 *f)
+{
+	if (rn->saddr)
+		rn->saddr[i] = f->saddr;
+	if (rn->daddr)
+		rn->daddr[i] = f->daddr;
+	if (rn->sport)
+		rn->sport[i] = f->sport;
+	if (rn->applied)
+		rn->applied[i] = f->applied;
+}
+
+struct rn_frame6 { uint8_t saddr[16]; uint16_t sport; uint8_t applied; };
+
+/* lb6_rev_nat (lb.h:305-317) + __lb6_rev_nat (:254-294), flags 0 */
+static void rn6_rev_nat(const or_ctx *c, uint16_t index, uint8_t nexthdr, struct rn_frame6 *f)
+{
+	const struct or_rn6 *nat = &c->rn6[index];
+	if (!nat->present)
+		return;
+	if (nat->port && (nexthdr == PROTO_TCP || nexthdr == PROTO_UDP))
+		f->sport = nat->port;
+	memcpy(f->saddr, nat->address, 16);
+	f->applied = 1;
+}
+
+/* egress bpf_lxc.c:222-235 (case CT_RELATED / CT_REPLY with an index);
+ * ingress :778-785: whatever ct_lookup6 returned, if the entry it hit has an
+ * index (a CT_NEW packet's ct_state stays zeroed) */
+static void rn6_site(const or_ctx *c, int egress, int ret, const struct ct_hit *st, uint8_t nexthdr,
+		     struct rn_frame6 *f)
+{
+	if (egress) {
+		if ((ret == 2 || ret == 3) && st->rev_nat)
+			rn6_rev_nat(c, st->rev_nat, nexthdr, f);
+	} else if (st->rev_nat) {
+		rn6_rev_nat(c, st->rev_nat, nexthdr, f);
+	}
+}
+
+static void rn6_store(const or_rnat6_out *rn, size_t i, const struct rn_frame6 *f)
+{
+	if (rn->saddr16)
+		memcpy(rn->saddr16 + 16 * i, f->saddr, 16);
+	if (rn->sport)
+		rn->sport[i] = f->sport;
+	if (rn->applied)
+		rn->applied[i] = f->applied;
 }
 
 static void ct_reverse(struct ct_key *k)
@@ -2299,6 +2450,17 @@ int or_classify_v4_ct(or_ctx *c, size_t n, const uint32_t *saddr, const uint32_t
 		      const uint16_t *ep, uint32_t now, int32_t *verdict, uint8_t *ct_ret,
 		      uint32_t *identity, uint8_t *stage, uint64_t *probe_sum)
 {
+	return or_classify_v4_ct_rnat(c, n, saddr, daddr, sport, dport, proto, l4b, flags, len, ep, now,
+				      verdict, ct_ret, identity, stage, NULL, probe_sum);
+}
+
+int or_classify_v4_ct_rnat(or_ctx *c, size_t n, const uint32_t *saddr, const uint32_t *daddr,
+			   const uint16_t *sport, const uint16_t *dport, const uint8_t *proto,
+			   const uint16_t *l4b, const uint8_t *flags, const uint32_t *len,
+			   const uint16_t *ep, uint32_t now, int32_t *verdict, uint8_t *ct_ret,
+			   uint32_t *identity, uint8_t *stage, const or_rnat4_out *rn,
+			   uint64_t *probe_sum)
+{
 	const or_config *cfg = &c->cfg;
 	uint64_t ops = 0;
 	for (size_t i = 0; i < n; i++) {
@@ -2313,6 +2475,7 @@ int or_classify_v4_ct(or_ctx *c, size_t n, const uint32_t *saddr, const uint32_t
 		int32_t v, fin;
 		uint32_t id;
 		struct pol_res r;
+		struct ct_hit hit = { 0, 0 }; /* struct ct_state ct_state = {} */
 
 		/* ct_lookup4, conntrack.h:441-561 */
 		k.daddr = daddr[i];
@@ -2350,16 +2513,20 @@ int or_classify_v4_ct(or_ctx *c, size_t n, const uint32_t *saddr, const uint32_t
 				stage[i] = 4;
 			c->metrics[(137 * 4 + mdir) * 2] += 1;
 			c->metrics[(137 * 4 + mdir) * 2 + 1] += len[i];
+			if (rn) { /* dropped by ct_lookup4: the frame as it came */
+				struct rn_frame4 f = { saddr[i], daddr[i], sport[i], 0 };
+				rn4_store(rn, i, &f);
+			}
 			continue;
 		}
 		ops += 1;
-		if (ct_lookup_one(c, &k, action, dir, tcp, w, len[i], now)) {
+		if (ct_lookup_one(c, &k, action, dir, tcp, w, len[i], now, &hit)) {
 			ret = (k.flags & TUPLE_F_RELATED) ? CT_RELATED : CT_REPLY;
 		} else {
 			ct_reverse(&k);
 			ops += 1;
-			ret = ct_lookup_one(c, &k, action, dir, tcp, w, len[i], now) ? CT_ESTABLISHED
-											 : CT_NEW;
+			ret = ct_lookup_one(c, &k, action, dir, tcp, w, len[i], now, &hit) ? CT_ESTABLISHED
+											       : CT_NEW;
 		}
 
 		if (egress) { /* bpf_lxc.c:484-500 */
@@ -2423,6 +2590,14 @@ int or_classify_v4_ct(or_ctx *c, size_t n, const uint32_t *saddr, const uint32_t
 			identity[i] = id;
 		if (stage)
 			stage[i] = (uint8_t)r.stage;
+		if (rn) {
+			/* the ingress site runs before the policy lookup, the egress one
+			 * after it, where a REPLY / RELATED packet is never dropped:
+			 * nothing after either site depends on it or undoes it */
+			struct rn_frame4 f = { saddr[i], daddr[i], sport[i], 0 };
+			rn4_site(c, egress, ret, &hit, pr, &f);
+			rn4_store(rn, i, &f);
+		}
 		if (fin <= 0) { /* a proxy redirect traces TRACE_TO_PROXY: no metrics */
 			uint32_t reason = fin < 0 ? (uint32_t)(-fin) & 0xff : 0;
 			c->metrics[(reason * 4 + mdir) * 2] += 1;
@@ -2569,6 +2744,18 @@ int or_classify_v4_ctlb(or_ctx *c, size_t n, const uint32_t *saddr, const uint32
 			uint8_t *ct_ret, uint32_t *identity, uint8_t *stage, uint32_t *xdaddr,
 			uint16_t *xdport, uint64_t *probe_sum)
 {
+	return or_classify_v4_ctlb_rnat(c, n, saddr, daddr, sport, dport, proto, l4b, flags, len, ep, hash,
+					now, verdict, ct_ret, identity, stage, xdaddr, xdport, NULL,
+					probe_sum);
+}
+
+int or_classify_v4_ctlb_rnat(or_ctx *c, size_t n, const uint32_t *saddr, const uint32_t *daddr,
+			     const uint16_t *sport, const uint16_t *dport, const uint8_t *proto,
+			     const uint16_t *l4b, const uint8_t *flags, const uint32_t *len,
+			     const uint16_t *ep, const uint32_t *hash, uint32_t now, int32_t *verdict,
+			     uint8_t *ct_ret, uint32_t *identity, uint8_t *stage, uint32_t *xdaddr,
+			     uint16_t *xdport, const or_rnat4_out *rn, uint64_t *probe_sum)
+{
 	const or_config *cfg = &c->cfg;
 	uint64_t ops = 0;
 	for (size_t i = 0; i < n; i++) {
@@ -2579,6 +2766,10 @@ int or_classify_v4_ctlb(or_ctx *c, size_t n, const uint32_t *saddr, const uint32
 		struct ohash *h = ep[i] < c->n_ep ? &c->policy[ep[i]] : NULL;
 		struct ct_st st;
 		struct ct_key k;
+		/* ct_state of the CT_EGRESS / CT_INGRESS lookup (bpf_lxc.c:421, :870),
+		 * not ct_state_new, which the service step fills */
+		struct ct_hit hit = { 0, 0 };
+		uint32_t fsaddr = saddr[i]; /* the frame's saddr (lb4_xlate may set it) */
 		uint32_t fdaddr = daddr[i], id = 0;
 		uint16_t fdport = dport[i], w;
 		int32_t v, fin = 0;
@@ -2649,6 +2840,7 @@ int or_classify_v4_ctlb(or_ctx *c, size_t n, const uint32_t *saddr, const uint32
 				st.addr = lbv_target(be);
 				fdaddr = lbv_target(be);
 				if (saddr[i] == lbv_target(be)) { /* loopback (lb.h:753-767) */
+					fsaddr = cfg->ipv4_loopback; /* lb4_xlate: new_saddr (lb.h:668-675) */
 					st.loopback = 1;
 					st.addr = cfg->ipv4_loopback;
 					st.svc_addr = saddr[i];
@@ -2671,12 +2863,12 @@ int or_classify_v4_ctlb(or_ctx *c, size_t n, const uint32_t *saddr, const uint32
 		{
 			const uint32_t orig_dip = k.daddr;
 			ops += 1;
-			if (ct_lookup_one(c, &k, action, dir, pr == PROTO_TCP, w, len[i], now)) {
+			if (ct_lookup_one(c, &k, action, dir, pr == PROTO_TCP, w, len[i], now, &hit)) {
 				ret = (k.flags & TUPLE_F_RELATED) ? CT_RELATED : CT_REPLY;
 			} else {
 				ct_reverse(&k);
 				ops += 1;
-				ret = ct_lookup_one(c, &k, action, dir, pr == PROTO_TCP, w, len[i], now)
+				ret = ct_lookup_one(c, &k, action, dir, pr == PROTO_TCP, w, len[i], now, &hit)
 					      ? CT_ESTABLISHED
 					      : CT_NEW;
 			}
@@ -2729,8 +2921,8 @@ int or_classify_v4_ctlb(or_ctx *c, size_t n, const uint32_t *saddr, const uint32
 				st.src_sec_id = egress ? sec : id;
 				cr = ct_create_st(c, &k, dir, &st, len[i], now, &ops);
 			}
-			/* CT_REPLY / CT_RELATED with rev_nat_index: lb4_rev_nat through the
-			 * empty cilium_lb4_reverse_nat map, a no-op (lb.h:562-576) */
+			/* CT_REPLY / CT_RELATED with rev_nat_index: lb4_rev_nat changes the
+			 * frame only (lb.h:562-576); reported at out: when rn is given */
 			if (cr < 0)
 				fin = cr;
 			else if (v > 0 && (egress || ret == CT_NEW || ret == CT_ESTABLISHED))
@@ -2754,6 +2946,15 @@ int or_classify_v4_ctlb(or_ctx *c, size_t n, const uint32_t *saddr, const uint32
 			xdaddr[i] = fdaddr;
 		if (xdport)
 			xdport[i] = fdport;
+		if (rn) {
+			/* the frame after lb4_xlate (daddr the backend, saddr IPV4_LOOPBACK
+			 * when the backend is the sender); a drop before ct_lookup4
+			 * (ret 255) leaves it as it is */
+			struct rn_frame4 f = { fsaddr, fdaddr, sport[i], 0 };
+			if (ret != 255)
+				rn4_site(c, egress, ret, &hit, pr, &f);
+			rn4_store(rn, i, &f);
+		}
 		if (fin <= 0) {
 			uint32_t reason = fin < 0 ? (uint32_t)(-fin) & 0xff : 0;
 			c->metrics[(reason * 4 + mdir) * 2] += 1;
@@ -2992,6 +3193,17 @@ int or_classify_v6_ct(or_ctx *c, size_t n, const uint8_t *saddr16, const uint8_t
 		      const uint16_t *ep, uint32_t now, int32_t *verdict, uint8_t *ct_ret,
 		      uint32_t *identity, uint8_t *stage, uint64_t *probe_sum)
 {
+	return or_classify_v6_ct_rnat(c, n, saddr16, daddr16, sport, dport, proto, l4b, flags, len, ep, now,
+				      verdict, ct_ret, identity, stage, NULL, probe_sum);
+}
+
+int or_classify_v6_ct_rnat(or_ctx *c, size_t n, const uint8_t *saddr16, const uint8_t *daddr16,
+			   const uint16_t *sport, const uint16_t *dport, const uint8_t *proto,
+			   const uint16_t *l4b, const uint8_t *flags, const uint32_t *len,
+			   const uint16_t *ep, uint32_t now, int32_t *verdict, uint8_t *ct_ret,
+			   uint32_t *identity, uint8_t *stage, const or_rnat6_out *rn,
+			   uint64_t *probe_sum)
+{
 	const or_config *cfg = &c->cfg;
 	uint64_t ops = 0;
 	for (size_t i = 0; i < n; i++) {
@@ -3007,6 +3219,7 @@ int or_classify_v6_ct(or_ctx *c, size_t n, const uint8_t *saddr16, const uint8_t
 		int32_t v, fin;
 		uint32_t id;
 		struct pol_res r;
+		struct ct_hit hit = { 0, 0 };
 
 		memset(&k, 0, sizeof(k));
 		memcpy(k.daddr, da, 16);
@@ -3045,15 +3258,22 @@ int or_classify_v6_ct(or_ctx *c, size_t n, const uint8_t *saddr16, const uint8_t
 				stage[i] = 4;
 			c->metrics[(137 * 4 + mdir) * 2] += 1;
 			c->metrics[(137 * 4 + mdir) * 2 + 1] += len[i];
+			if (rn) {
+				struct rn_frame6 f;
+				memcpy(f.saddr, sa, 16);
+				f.sport = sport[i];
+				f.applied = 0;
+				rn6_store(rn, i, &f);
+			}
 			continue;
 		}
 		ops += 1;
-		if (ct_lookup_kb(&c->ct6, (const uint8_t *)&k, action, dir, tcp, w, len[i], now)) {
+		if (ct_lookup_hit(&c->ct6, (const uint8_t *)&k, action, dir, tcp, w, len[i], now, &hit)) {
 			ret = (k.flags & TUPLE_F_RELATED) ? CT_RELATED : CT_REPLY;
 		} else {
 			ct6_reverse(&k);
 			ops += 1;
-			ret = ct_lookup_kb(&c->ct6, (const uint8_t *)&k, action, dir, tcp, w, len[i], now)
+			ret = ct_lookup_hit(&c->ct6, (const uint8_t *)&k, action, dir, tcp, w, len[i], now, &hit)
 				      ? CT_ESTABLISHED : CT_NEW;
 		}
 
@@ -3117,6 +3337,17 @@ int or_classify_v6_ct(or_ctx *c, size_t n, const uint8_t *saddr16, const uint8_t
 			identity[i] = id;
 		if (stage)
 			stage[i] = (uint8_t)r.stage;
+		if (rn) {
+			/* ingress: straight after ct_lookup6, before the policy lookup
+			 * (bpf_lxc.c:778-785), so a packet the policy then drops has been
+			 * rewritten too; egress: in the switch after it (:222-235) */
+			struct rn_frame6 f;
+			memcpy(f.saddr, sa, 16);
+			f.sport = sport[i];
+			f.applied = 0;
+			rn6_site(c, egress, ret, &hit, pr, &f);
+			rn6_store(rn, i, &f);
+		}
 		if (fin <= 0) {
 			uint32_t reason = fin < 0 ? (uint32_t)(-fin) & 0xff : 0;
 			c->metrics[(reason * 4 + mdir) * 2] += 1;
@@ -3216,6 +3447,18 @@ int or_classify_v6_ctlb(or_ctx *c, size_t n, const uint8_t *saddr16, const uint8
 			uint8_t *ct_ret, uint32_t *identity, uint8_t *stage, uint8_t *xdaddr16,
 			uint16_t *xdport, uint64_t *probe_sum)
 {
+	return or_classify_v6_ctlb_rnat(c, n, saddr16, daddr16, sport, dport, proto, l4b, flags, len, ep, hash,
+					now, verdict, ct_ret, identity, stage, xdaddr16, xdport, NULL,
+					probe_sum);
+}
+
+int or_classify_v6_ctlb_rnat(or_ctx *c, size_t n, const uint8_t *saddr16, const uint8_t *daddr16,
+			     const uint16_t *sport, const uint16_t *dport, const uint8_t *proto,
+			     const uint16_t *l4b, const uint8_t *flags, const uint32_t *len,
+			     const uint16_t *ep, const uint32_t *hash, uint32_t now, int32_t *verdict,
+			     uint8_t *ct_ret, uint32_t *identity, uint8_t *stage, uint8_t *xdaddr16,
+			     uint16_t *xdport, const or_rnat6_out *rn, uint64_t *probe_sum)
+{
 	const or_config *cfg = &c->cfg;
 	uint64_t ops = 0;
 	for (size_t i = 0; i < n; i++) {
@@ -3233,6 +3476,7 @@ int or_classify_v6_ctlb(or_ctx *c, size_t n, const uint8_t *saddr16, const uint8
 		int32_t v, fin = 0;
 		int action, ret = 255, pstage = 0;
 		struct pol_res r;
+		struct ct_hit hit = { 0, 0 }; /* ct_state, not ct_state_new */
 
 		memset(&st, 0, sizeof(st));
 		memset(&k, 0, sizeof(k));
@@ -3315,13 +3559,14 @@ int or_classify_v6_ctlb(or_ctx *c, size_t n, const uint8_t *saddr16, const uint8
 			uint8_t orig_dip[16];
 			memcpy(orig_dip, k.daddr, 16);
 			ops += 1;
-			if (ct_lookup_kb(&c->ct6, (const uint8_t *)&k, action, dir, pr == PROTO_TCP, w, len[i], now)) {
+			if (ct_lookup_hit(&c->ct6, (const uint8_t *)&k, action, dir, pr == PROTO_TCP, w, len[i], now,
+					  &hit)) {
 				ret = (k.flags & TUPLE_F_RELATED) ? CT_RELATED : CT_REPLY;
 			} else {
 				ct6_reverse(&k);
 				ops += 1;
-				ret = ct_lookup_kb(&c->ct6, (const uint8_t *)&k, action, dir, pr == PROTO_TCP, w, len[i],
-						   now)
+				ret = ct_lookup_hit(&c->ct6, (const uint8_t *)&k, action, dir, pr == PROTO_TCP, w, len[i],
+						    now, &hit)
 					      ? CT_ESTABLISHED
 					      : CT_NEW;
 			}
@@ -3395,6 +3640,15 @@ int or_classify_v6_ctlb(or_ctx *c, size_t n, const uint8_t *saddr16, const uint8
 			memcpy(xdaddr16 + 16 * i, fdaddr, 16);
 		if (xdport)
 			xdport[i] = fdport;
+		if (rn) { /* lb6_xlate leaves the frame's saddr and sport alone */
+			struct rn_frame6 f;
+			memcpy(f.saddr, sa, 16);
+			f.sport = sport[i];
+			f.applied = 0;
+			if (ret != 255)
+				rn6_site(c, egress, ret, &hit, pr, &f);
+			rn6_store(rn, i, &f);
+		}
 		if (fin <= 0) {
 			uint32_t reason = fin < 0 ? (uint32_t)(-fin) & 0xff : 0;
 			c->metrics[(reason * 4 + mdir) * 2] += 1;

@@ -273,6 +273,77 @@ int or_classify_v6_ctlb(or_ctx *c, size_t n, const uint8_t *saddr16, const uint8
 			uint16_t *xdport, uint64_t *probe_sum);
 
 /*
+ * Reverse NAT of service replies.  The maps cilium_lb4_reverse_nat /
+ * cilium_lb6_reverse_nat: the key is the raw __u16 as a service entry's
+ * rev_nat_index holds it, the value struct lb4_reverse_nat (6 B: address,
+ * port) / lb6_reverse_nat (18 B), bpf/lib/common.h.  update is BPF_ANY;
+ * delete of an absent index -ENOENT.  A shard view shares its base's maps.
+ */
+int or_revnat4_update(or_ctx *c, uint16_t index, const void *val6);
+int or_revnat4_delete(or_ctx *c, uint16_t index);
+int or_revnat6_update(or_ctx *c, uint16_t index, const void *val18);
+int or_revnat6_delete(or_ctx *c, uint16_t index);
+
+/*
+ * The frame's source (IPv4: and destination) fields as the endpoint program
+ * leaves them, per packet; every column may be NULL.  The frame starts as the
+ * input, on the _ctlb paths as lb4_xlate / lb6_xlate left it (daddr the
+ * backend; IPv4 saddr IPV4_LOOPBACK when the backend is the sender,
+ * lb.h:761-766, :668-675), and changes where the program calls lb4_rev_nat /
+ * lb6_rev_nat with the ct_state that ct_lookup4 / ct_lookup6 (CT_EGRESS /
+ * CT_INGRESS) filled from the entry the packet hit (conntrack.h:213-217),
+ * never the ct_state_new of the service step:
+ *   IPv4 egress  bpf_lxc.c:531-541  CT_REPLY / CT_RELATED, rev_nat_index != 0
+ *   IPv4 ingress bpf_lxc.c:909-918  CT_REPLY, rev_nat_index != 0, !loopback
+ *   IPv6 egress  bpf_lxc.c:222-235  CT_REPLY / CT_RELATED, rev_nat_index != 0
+ *   IPv6 ingress bpf_lxc.c:778-785  rev_nat_index != 0, whatever ct_lookup6
+ *                                   returned (a CT_NEW packet's is 0)
+ * applied: the map held the index and __lb4_rev_nat (lb.h:485-550) /
+ * __lb6_rev_nat (:254-294) ran: sport := nat->port for TCP / UDP when the
+ * port is nonzero (reverse_map_l4_port, :218-252), IPv4 with ct_state.loopback
+ * daddr := the old saddr, saddr := nat->address.  A packet dropped before
+ * ct_lookup keeps its frame.  Checksums are not modelled, and the map lookup
+ * is not counted in *probe_sum.
+ */
+typedef struct or_rnat4_out {
+	uint32_t *saddr, *daddr;
+	uint16_t *sport;
+	uint8_t *applied;
+} or_rnat4_out;
+typedef struct or_rnat6_out {
+	uint8_t *saddr16;
+	uint16_t *sport;
+	uint8_t *applied;
+} or_rnat6_out;
+
+/* The four stateful calls with that output; rn == NULL: exactly those calls
+ * (they forward here), which never read the two maps. */
+int or_classify_v4_ct_rnat(or_ctx *c, size_t n, const uint32_t *saddr, const uint32_t *daddr,
+			   const uint16_t *sport, const uint16_t *dport, const uint8_t *proto,
+			   const uint16_t *l4b, const uint8_t *flags, const uint32_t *len,
+			   const uint16_t *ep, uint32_t now, int32_t *verdict, uint8_t *ct_ret,
+			   uint32_t *identity, uint8_t *stage, const or_rnat4_out *rn,
+			   uint64_t *probe_sum);
+int or_classify_v4_ctlb_rnat(or_ctx *c, size_t n, const uint32_t *saddr, const uint32_t *daddr,
+			     const uint16_t *sport, const uint16_t *dport, const uint8_t *proto,
+			     const uint16_t *l4b, const uint8_t *flags, const uint32_t *len,
+			     const uint16_t *ep, const uint32_t *hash, uint32_t now, int32_t *verdict,
+			     uint8_t *ct_ret, uint32_t *identity, uint8_t *stage, uint32_t *xdaddr,
+			     uint16_t *xdport, const or_rnat4_out *rn, uint64_t *probe_sum);
+int or_classify_v6_ct_rnat(or_ctx *c, size_t n, const uint8_t *saddr16, const uint8_t *daddr16,
+			   const uint16_t *sport, const uint16_t *dport, const uint8_t *proto,
+			   const uint16_t *l4b, const uint8_t *flags, const uint32_t *len,
+			   const uint16_t *ep, uint32_t now, int32_t *verdict, uint8_t *ct_ret,
+			   uint32_t *identity, uint8_t *stage, const or_rnat6_out *rn,
+			   uint64_t *probe_sum);
+int or_classify_v6_ctlb_rnat(or_ctx *c, size_t n, const uint8_t *saddr16, const uint8_t *daddr16,
+			     const uint16_t *sport, const uint16_t *dport, const uint8_t *proto,
+			     const uint16_t *l4b, const uint8_t *flags, const uint32_t *len,
+			     const uint16_t *ep, const uint32_t *hash, uint32_t now, int32_t *verdict,
+			     uint8_t *ct_ret, uint32_t *identity, uint8_t *stage, uint8_t *xdaddr16,
+			     uint16_t *xdport, const or_rnat6_out *rn, uint64_t *probe_sum);
+
+/*
  * L3 MapState compilation: the tables of cgpu.h
  * cgpu_l3_program / cgpu_label_sets (interned ids, see cilium_amd/policy.py);
  * allow[e * n_id + i] bit 0 = ingress Allowed, bit 1 = egress Allowed.

@@ -28,8 +28,28 @@ class OrConfig(C.Structure):
     ]
 
 
+class OrRnat4Out(C.Structure):
+    _fields_ = [("saddr", C.c_void_p), ("daddr", C.c_void_p), ("sport", C.c_void_p), ("applied", C.c_void_p)]
+
+
+class OrRnat6Out(C.Structure):
+    _fields_ = [("saddr16", C.c_void_p), ("sport", C.c_void_p), ("applied", C.c_void_p)]
+
+
+SOURCES = ("cgpu_oracle.c", "cgpu_oracle.h", "fast_lpm.h")
+
+
 def build():
     subprocess.run(["make", "-s", "-C", HERE], check=True)
+
+
+def _stale():
+    """The library is missing or older than a source it is built from (an
+    earlier build left in the tree must not answer for newer sources)."""
+    if not os.path.exists(LIB_PATH):
+        return True
+    built = os.path.getmtime(LIB_PATH)
+    return any(os.path.getmtime(os.path.join(HERE, f)) > built for f in SOURCES)
 
 
 _lib = None
@@ -38,7 +58,7 @@ _lib = None
 def lib():
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
+        if _stale():
             build()
         L = C.CDLL(LIB_PATH)
         vp, sz = C.c_void_p, C.c_size_t
@@ -109,6 +129,18 @@ def lib():
             C.POINTER(C.c_uint64)]
         L.or_classify_v6_ct.argtypes = [vp, sz] + [vp] * 9 + [C.c_uint32] + [vp] * 4 + [
             C.POINTER(C.c_uint64)]
+        for f in ("or_revnat4_update", "or_revnat6_update"):
+            getattr(L, f).argtypes = [vp, C.c_uint16, vp]
+        for f in ("or_revnat4_delete", "or_revnat6_delete"):
+            getattr(L, f).argtypes = [vp, C.c_uint16]
+        L.or_classify_v4_ct_rnat.argtypes = [vp, sz] + [vp] * 9 + [C.c_uint32] + [vp] * 4 + [
+            C.POINTER(OrRnat4Out), C.POINTER(C.c_uint64)]
+        L.or_classify_v6_ct_rnat.argtypes = [vp, sz] + [vp] * 9 + [C.c_uint32] + [vp] * 4 + [
+            C.POINTER(OrRnat6Out), C.POINTER(C.c_uint64)]
+        L.or_classify_v4_ctlb_rnat.argtypes = [vp, sz] + [vp] * 10 + [C.c_uint32] + [vp] * 6 + [
+            C.POINTER(OrRnat4Out), C.POINTER(C.c_uint64)]
+        L.or_classify_v6_ctlb_rnat.argtypes = [vp, sz] + [vp] * 10 + [C.c_uint32] + [vp] * 6 + [
+            C.POINTER(OrRnat6Out), C.POINTER(C.c_uint64)]
         u32 = C.c_uint32
         L.or_l3_compile.argtypes = [vp, vp, vp, vp, vp, u32, vp, vp, vp, u32, vp, vp, u32, u32, vp]
         L.or_view_create.argtypes = [vp]
@@ -415,7 +447,33 @@ class Oracle:
     def ct4_gc(self, time):
         return self.L.or_ct4_gc(self.h, time)
 
-    def classify_v4_ct(self, t, now):
+    # --- reverse NAT maps (cilium_lb4_reverse_nat / cilium_lb6_reverse_nat) ---
+    def revnat4_update(self, index, val):
+        """index: the raw u16 as a service entry's rev_nat_index holds it"""
+        return self.L.or_revnat4_update(self.h, index, _b(val))
+
+    def revnat4_delete(self, index):
+        return self.L.or_revnat4_delete(self.h, index)
+
+    def revnat6_update(self, index, val):
+        return self.L.or_revnat6_update(self.h, index, _b(val))
+
+    def revnat6_delete(self, index):
+        return self.L.or_revnat6_delete(self.h, index)
+
+    @staticmethod
+    def _rnat(v6, n):
+        """The rev_nat=True columns (named as the engine's) and their struct."""
+        rn = {"rn_saddr": np.empty((n, 16), np.uint8) if v6 else np.empty(n, np.uint32),
+              "rn_sport": np.empty(n, np.uint16), "rn_applied": np.empty(n, np.uint8)}
+        if v6:
+            return rn, OrRnat6Out(*[rn[k].ctypes.data for k in ("rn_saddr", "rn_sport", "rn_applied")])
+        rn["rn_daddr"] = np.empty(n, np.uint32)
+        return rn, OrRnat4Out(*[rn[k].ctypes.data for k in ("rn_saddr", "rn_daddr", "rn_sport", "rn_applied")])
+
+    def classify_v4_ct(self, t, now, rev_nat=False):
+        """rev_nat=True (or_classify_v4_ct_rnat): a sixth element, the dict of
+        rn_saddr / rn_daddr / rn_sport / rn_applied."""
         n = len(t["saddr"])
         verdict = np.empty(n, np.int32)
         ct_ret = np.empty(n, np.uint8)
@@ -426,14 +484,22 @@ class Oracle:
             ("saddr", np.uint32), ("daddr", np.uint32), ("sport", np.uint16),
             ("dport", np.uint16), ("proto", np.uint8), ("l4b", np.uint16), ("flags", np.uint8),
             ("len", np.uint32), ("ep", np.uint16))]
+        if rev_nat:
+            rn, rs = self._rnat(False, n)
+            rc = self.L.or_classify_v4_ct_rnat(self.h, n, *[_p(a) for a in arrs], now, _p(verdict),
+                                               _p(ct_ret), _p(identity), _p(stage), C.byref(rs),
+                                               C.byref(probes))
+            assert rc == 0, rc
+            return verdict, ct_ret, identity, stage, probes.value, rn
         rc = self.L.or_classify_v4_ct(self.h, n, *[_p(a) for a in arrs], now, _p(verdict),
                                       _p(ct_ret), _p(identity), _p(stage), C.byref(probes))
         assert rc == 0, rc
         return verdict, ct_ret, identity, stage, probes.value
 
-    def classify_v4_ctlb(self, t, now):
+    def classify_v4_ctlb(self, t, now, rev_nat=False):
         """or_classify_v4_ctlb: the stateful service step + conntrack; t as
-        classify_v4_ct plus an optional "hash" column (skb->hash)."""
+        classify_v4_ct plus an optional "hash" column (skb->hash).
+        rev_nat=True (or_classify_v4_ctlb_rnat): the rn_* columns too."""
         n = len(t["saddr"])
         out = {"verdict": np.empty(n, np.int32), "ct_ret": np.empty(n, np.uint8),
                "identity": np.empty(n, np.uint32), "stage": np.empty(n, np.uint8),
@@ -444,11 +510,20 @@ class Oracle:
             ("dport", np.uint16), ("proto", np.uint8), ("l4b", np.uint16), ("flags", np.uint8),
             ("len", np.uint32), ("ep", np.uint16))]
         h = np.ascontiguousarray(t["hash"], np.uint32) if t.get("hash") is not None else None
-        rc = self.L.or_classify_v4_ctlb(self.h, n, *[_p(a) for a in arrs],
-                                        None if h is None else _p(h), now,
-                                        *[_p(out[k]) for k in ("verdict", "ct_ret", "identity",
-                                                               "stage", "xdaddr", "xdport")],
-                                        C.byref(probes))
+        if rev_nat:
+            rn, rs = self._rnat(False, n)
+            rc = self.L.or_classify_v4_ctlb_rnat(self.h, n, *[_p(a) for a in arrs],
+                                                 None if h is None else _p(h), now,
+                                                 *[_p(out[k]) for k in ("verdict", "ct_ret", "identity",
+                                                                        "stage", "xdaddr", "xdport")],
+                                                 C.byref(rs), C.byref(probes))
+            out.update(rn)
+        else:
+            rc = self.L.or_classify_v4_ctlb(self.h, n, *[_p(a) for a in arrs],
+                                            None if h is None else _p(h), now,
+                                            *[_p(out[k]) for k in ("verdict", "ct_ret", "identity",
+                                                                   "stage", "xdaddr", "xdport")],
+                                            C.byref(probes))
         assert rc == 0, rc
         out["probes"] = probes.value
         return out
@@ -483,7 +558,9 @@ class Oracle:
     def ct6_gc(self, time):
         return self.L.or_ct6_gc(self.h, time)
 
-    def classify_v6_ct(self, t, now):
+    def classify_v6_ct(self, t, now, rev_nat=False):
+        """rev_nat=True (or_classify_v6_ct_rnat): a sixth element, the dict of
+        rn_saddr (n, 16) / rn_sport / rn_applied."""
         n = len(t["saddr"])
         verdict = np.empty(n, np.int32)
         ct_ret = np.empty(n, np.uint8)
@@ -494,14 +571,22 @@ class Oracle:
             ("saddr", np.uint8), ("daddr", np.uint8), ("sport", np.uint16),
             ("dport", np.uint16), ("proto", np.uint8), ("l4b", np.uint16), ("flags", np.uint8),
             ("len", np.uint32), ("ep", np.uint16))]
+        if rev_nat:
+            rn, rs = self._rnat(True, n)
+            rc = self.L.or_classify_v6_ct_rnat(self.h, n, *[_p(a) for a in arrs], now, _p(verdict),
+                                               _p(ct_ret), _p(identity), _p(stage), C.byref(rs),
+                                               C.byref(probes))
+            assert rc == 0, rc
+            return verdict, ct_ret, identity, stage, probes.value, rn
         rc = self.L.or_classify_v6_ct(self.h, n, *[_p(a) for a in arrs], now, _p(verdict),
                                       _p(ct_ret), _p(identity), _p(stage), C.byref(probes))
         assert rc == 0, rc
         return verdict, ct_ret, identity, stage, probes.value
 
-    def classify_v6_ctlb(self, t, now):
+    def classify_v6_ctlb(self, t, now, rev_nat=False):
         """or_classify_v6_ctlb: classify_v6_ct with the stateful service
-        step; t may carry a "hash" column.  xdaddr is (n, 16) uint8."""
+        step; t may carry a "hash" column.  xdaddr is (n, 16) uint8.
+        rev_nat=True (or_classify_v6_ctlb_rnat): the rn_* columns too."""
         n = len(t["saddr"])
         out = {"verdict": np.empty(n, np.int32), "ct_ret": np.empty(n, np.uint8),
                "identity": np.empty(n, np.uint32), "stage": np.empty(n, np.uint8),
@@ -512,11 +597,20 @@ class Oracle:
             ("dport", np.uint16), ("proto", np.uint8), ("l4b", np.uint16), ("flags", np.uint8),
             ("len", np.uint32), ("ep", np.uint16))]
         h = np.ascontiguousarray(t["hash"], np.uint32) if t.get("hash") is not None else None
-        rc = self.L.or_classify_v6_ctlb(self.h, n, *[_p(a) for a in arrs],
-                                        None if h is None else _p(h), now,
-                                        *[_p(out[k]) for k in ("verdict", "ct_ret", "identity",
-                                                               "stage", "xdaddr", "xdport")],
-                                        C.byref(probes))
+        if rev_nat:
+            rn, rs = self._rnat(True, n)
+            rc = self.L.or_classify_v6_ctlb_rnat(self.h, n, *[_p(a) for a in arrs],
+                                                 None if h is None else _p(h), now,
+                                                 *[_p(out[k]) for k in ("verdict", "ct_ret", "identity",
+                                                                        "stage", "xdaddr", "xdport")],
+                                                 C.byref(rs), C.byref(probes))
+            out.update(rn)
+        else:
+            rc = self.L.or_classify_v6_ctlb(self.h, n, *[_p(a) for a in arrs],
+                                            None if h is None else _p(h), now,
+                                            *[_p(out[k]) for k in ("verdict", "ct_ret", "identity",
+                                                                   "stage", "xdaddr", "xdport")],
+                                            C.byref(probes))
         assert rc == 0, rc
         out["probes"] = probes.value
         return out

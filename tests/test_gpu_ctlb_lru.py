@@ -124,15 +124,25 @@ def _lru_engine(W, ct_max, lru=1):
     return e
 
 
-def _run(torch, e, F, t, now):
-    out = getattr(e, F.run)(synth.to_device(t), now)
+def _run(torch, e, F, t, now, rev_nat=False):
+    """rev_nat=True: the _rnat call, and its rn_* columns in the result too."""
+    out = getattr(e, F.run)(synth.to_device(t), now, rev_nat=True) if rev_nat else \
+        getattr(e, F.run)(synth.to_device(t), now)
     torch.cuda.synchronize()
     xd = out["daddr"].cpu().numpy()
-    return {"verdict": out["verdict"].cpu().numpy(), "ct_ret": out["ct_ret"].cpu().numpy(),
-            "identity": out["identity"].cpu().numpy().view(np.uint32),
-            "stage": out["stage"].cpu().numpy(),
-            "xdaddr": xd if F.v6 else xd.view(np.uint32),
-            "xdport": out["dport"].cpu().numpy().view(np.uint16)}
+    res = {"verdict": out["verdict"].cpu().numpy(), "ct_ret": out["ct_ret"].cpu().numpy(),
+           "identity": out["identity"].cpu().numpy().view(np.uint32),
+           "stage": out["stage"].cpu().numpy(),
+           "xdaddr": xd if F.v6 else xd.view(np.uint32),
+           "xdport": out["dport"].cpu().numpy().view(np.uint16)}
+    if rev_nat:
+        sa = out["rn_saddr"].cpu().numpy()
+        res.update(rn_saddr=sa if F.v6 else sa.view(np.uint32),
+                   rn_sport=out["rn_sport"].cpu().numpy().view(np.uint16),
+                   rn_applied=out["rn_applied"].cpu().numpy())
+        if not F.v6:
+            res["rn_daddr"] = out["rn_daddr"].cpu().numpy().view(np.uint32)
+    return res
 
 
 def _same_results(out, exp, t, msg, mask=None):
@@ -152,17 +162,19 @@ def _maps(e, o, F, pre):
     return gb, ob, pb
 
 
-def _batch(torch, e, W, t, now, msg, o=None):
+def _batch(torch, e, W, t, now, msg, o=None, rev_nat=False):
     """One engine batch against the restatement started from the map the
     batch found (or the restatement `o`, already holding that map).  Checks
-    the results and the map; returns (out, exp, evictions of this batch)."""
+    the results and the map; returns (out, exp, evictions of this batch).
+    rev_nat=True: both sides run their _rnat call, out and exp carry the
+    rn_* columns (compared by the caller)."""
     F = W[0]
     pre = getattr(e, F.dump)()
     if o is None:
         o = _oracle(W, pre)
     ev0 = e.ct_lru_stats(F.v6)["evictions"]
-    out = _run(torch, e, F, t, now)
-    exp = getattr(o, F.run)(t, now)
+    out = _run(torch, e, F, t, now, rev_nat)
+    exp = getattr(o, F.run)(t, now, rev_nat=True) if rev_nat else getattr(o, F.run)(t, now)
     for name, code in (("DROP_CT_CREATE_FAILED", L.DROP_CT_CREATE_FAILED), ("DROP_NO_SERVICE", L.DROP_NO_SERVICE)):
         print(f"{msg}: engine {name} {(out['verdict'] == code).sum()}, restatement {(exp['verdict'] == code).sum()}")
     _same_results(out, exp, t, msg)
