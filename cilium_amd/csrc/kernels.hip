@@ -200,6 +200,140 @@ __device__ __forceinline__ uint4 pg_resolve(const pol_groups &t, uint4 g, uint32
 	return r;
 }
 
+/* All four words of a gathered slot are wanted here, whatever the branches
+ * below use of them: without this the compiler splits the 16-byte load of
+ * one tuple of a quad and moves the word that only some lanes need into
+ * their branch, a load of its own with its own wait. */
+__device__ __forceinline__ void whole_x4(uint4 &v)
+{
+	asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w));
+}
+/* the same for the slots of a quad, as one statement: the compiler cannot
+ * move one tuple's load behind another tuple's wait */
+template <int Q> __device__ __forceinline__ void whole_q(uint4 (&v)[Q])
+{
+	if constexpr (Q == 4) {
+		asm volatile(""
+			     : "+v"(v[0].x), "+v"(v[0].y), "+v"(v[0].z), "+v"(v[0].w), "+v"(v[1].x), "+v"(v[1].y),
+			       "+v"(v[1].z), "+v"(v[1].w), "+v"(v[2].x), "+v"(v[2].y), "+v"(v[2].z), "+v"(v[2].w),
+			       "+v"(v[3].x), "+v"(v[3].y), "+v"(v[3].z), "+v"(v[3].w));
+	} else {
+#pragma unroll
+		for (int u = 0; u < Q; u++)
+			whole_x4(v[u]);
+	}
+}
+
+/* One 16-byte gather per tuple of a quad, the Q loads back to back: every
+ * address is in registers before the first load (address arithmetic between
+ * the loads reuses registers that an earlier load still owes, which the
+ * compiler then waits for), and all the loaded words are wanted at once */
+template <int Q> __device__ __forceinline__ void gather_q(const uint4 *(&p)[Q], uint4 (&x)[Q])
+{
+	if constexpr (Q == 4)
+		asm volatile("" : "+v"(p[0]), "+v"(p[1]), "+v"(p[2]), "+v"(p[3]));
+	/* (device memory: the statement above hides where p points) */
+	typedef const __attribute__((address_space(1))) v4u_t *gx4;
+#pragma unroll
+	for (int u = 0; u < Q; u++) {
+		const v4u_t v = *(gx4)p[u];
+		x[u] = make_uint4(v.x, v.y, v.z, v.w);
+	}
+	whole_q<Q>(x);
+}
+
+/* pol_resolve1 over the Q tuples of a lane (k_classify_x4): want[u] tuples
+ * resolve {lo[u], hi[u], ep[u]} from their home slot sl[u] (index b[u]) into
+ * ctr[u] / z[u]; the others keep theirs.  The hop slots are read in rounds:
+ * every tuple that still has hop bits loads ONE candidate slot, all Q loads
+ * issued together and then compared, so a round is one round trip for the
+ * quad and not one per tuple and hop.  A tuple with no bits left loads slot 0
+ * (branch-free: a branch around a tuple's load makes the compiler wait for
+ * it before the next tuple's is issued).  A tuple's candidates come in the
+ * order of pol_resolve1 and its first match ends them.  The loop's condition
+ * is wave-uniform. */
+template <int Q>
+__device__ __forceinline__ void pol_resolve_q(const pol_table &t, const uint4 (&sl)[Q], const uint32_t (&b)[Q],
+					      const uint32_t (&lo)[Q], const uint32_t (&hi)[Q],
+					      const uint32_t (&ep)[Q], const bool (&want)[Q], int (&ctr)[Q],
+					      uint32_t (&z)[Q])
+{
+	const uint4 *tab = reinterpret_cast<const uint4 *>(t.slots);
+	uint32_t hop[Q], any = 0u;
+#pragma unroll
+	for (int u = 0; u < Q; u++) {
+		hop[u] = want[u] ? sl[u].w >> POL_HOP_SHIFT : 0u;
+		if ((hop[u] & 1u) && sl[u].x == lo[u] && sl[u].y == hi[u] && (sl[u].z & 0xFFFFu) == ep[u]) {
+			z[u] = sl[u].z;
+			ctr[u] = (int)(sl[u].w & POL_CTR_MASK);
+			hop[u] = 0u;
+		}
+		hop[u] &= ~1u;
+		any |= hop[u];
+	}
+	while (__ballot(any != 0u)) {
+		uint4 x[Q];
+		const uint4 *p[Q];
+#pragma unroll
+		for (int u = 0; u < Q; u++) {
+			const uint32_t j = hop[u] ? (uint32_t)__builtin_ctz(hop[u]) : 0u;
+			p[u] = tab + (hop[u] ? (b[u] + j) & t.bucket_mask : 0u);
+		}
+		gather_q<Q>(p, x);
+		any = 0u;
+#pragma unroll
+		for (int u = 0; u < Q; u++) {
+			const bool hit = hop[u] && x[u].x == lo[u] && x[u].y == hi[u] && (x[u].z & 0xFFFFu) == ep[u];
+			z[u] = hit ? x[u].z : z[u];
+			ctr[u] = hit ? (int)(x[u].w & POL_CTR_MASK) : ctr[u];
+			hop[u] = hit ? 0u : hop[u] & (hop[u] - 1u);
+			any |= hop[u];
+		}
+	}
+}
+
+/* pg_resolve over the Q tuples of a lane, in the rounds of pol_resolve_q:
+ * g[u] (home slot, index b[u]) becomes the group slot of {id[u], ed[u]} or
+ * {0, 0, EMPTY, 0}; tuples with want[u] clear keep theirs. */
+template <int Q>
+__device__ __forceinline__ void pg_resolve_q(const pol_groups &t, uint4 (&g)[Q], const uint32_t (&b)[Q],
+					     const uint32_t (&id)[Q], const uint32_t (&ed)[Q],
+					     const bool (&want)[Q])
+{
+	uint32_t hop[Q], any = 0u;
+#pragma unroll
+	for (int u = 0; u < Q; u++) {
+		hop[u] = want[u] ? g[u].y >> POL_HOP_SHIFT : 0u;
+		if ((hop[u] & 1u) && g[u].x == id[u] && (g[u].y & 0x1FFFFu) == ed[u])
+			hop[u] = 0u; /* the home slot itself */
+		else if (want[u])
+			g[u] = make_uint4(0, 0, POL_CTR_EMPTY, 0);
+		hop[u] &= ~1u;
+		any |= hop[u];
+	}
+	while (__ballot(any != 0u)) {
+		uint4 x[Q];
+		const uint4 *p[Q];
+#pragma unroll
+		for (int u = 0; u < Q; u++) {
+			const uint32_t j = hop[u] ? (uint32_t)__builtin_ctz(hop[u]) : 0u;
+			p[u] = t.slots + (hop[u] ? (b[u] + j) & t.mask : 0u);
+		}
+		gather_q<Q>(p, x);
+		any = 0u;
+#pragma unroll
+		for (int u = 0; u < Q; u++) {
+			const bool hit = hop[u] && x[u].x == id[u] && (x[u].y & 0x1FFFFu) == ed[u];
+			g[u].x = hit ? x[u].x : g[u].x;
+			g[u].y = hit ? x[u].y : g[u].y;
+			g[u].z = hit ? x[u].z : g[u].z;
+			g[u].w = hit ? x[u].w : g[u].w;
+			hop[u] = hit ? 0u : hop[u] & (hop[u] - 1u);
+			any |= hop[u];
+		}
+	}
+}
+
 __device__ __forceinline__ bool set4_has(const addr_set4 &t, uint32_t a)
 {
 	uint32_t b = mix32(a, 0x5e7) & t.bucket_mask;
@@ -1823,6 +1957,12 @@ __global__ __launch_bounds__(NT, MINW) void k_classify_x4(cgpu_snapshot s, cls_a
 							  tun_args ta)
 {
 	constexpr bool FF = FR == 2;
+	/* QX: the plain IPv4 tuple kernel.  Its gather stages are written
+	 * branch-free (a tuple that skips a stage loads a fixed in-range slot
+	 * and drops the value) and its hop slots are resolved across the quad
+	 * (pg_resolve_q, pol_resolve_q), so that a stage's Q loads are in flight
+	 * together; the other instantiations keep the per-tuple form */
+	constexpr bool QX = Q == 4 && !LB && !V6 && FR == 0 && !IPCE && !XDP && !TUN;
 	/* TUN (tun_args): with the pre-pass (IPCE) k_ipc6_pre writes the tunnels */
 	static_assert(!TUN || (FR == 0 && !IPCE), "the tunnel output: tuple columns, lookups in this kernel");
 	static_assert(!XDP || (LB && !V6), "the XDP prefilter: the IPv4 cascade");
@@ -2300,7 +2440,29 @@ __global__ __launch_bounds__(NT, MINW) void k_classify_x4(cgpu_snapshot s, cls_a
 #endif
 		} else {
 			/* v4: the /16's inline node (x16), then the compressed LPM */
-			{
+			if constexpr (QX) {
+				/* one 16-byte gather per tuple, the Q of them in flight
+				 * together: a tuple without a lookup reads slot 0 */
+				uint4 q[Q];
+				bool act[Q];
+#pragma unroll
+				for (int u = 0; u < Q; u++) {
+					act[u] = (fw[u] & (F_OK | F_GATED | F_LBDROP)) == F_OK;
+					q[u] = reinterpret_cast<const uint4 *>(
+						s.ipc4c.x16)[act[u] ? DIAG_LPM(bswap32(ad[u]) >> 16) : 0u];
+				}
+				whole_q<Q>(q);
+#pragma unroll
+				for (int u = 0; u < Q; u++) {
+					const bool inl = act[u] && !(q[u].w & LPMC_OVERFLOW);
+					const uint32_t x = bswap32(ad[u]) & 0xFFFFu;
+					const uint32_t cnt = (x >= (q[u].x & 0xFFFFu) ? 1u : 0u) + (x >= (q[u].x >> 16) ? 1u : 0u) +
+							     (x >= (q[u].y & 0xFFFFu) ? 1u : 0u) + (x >= (q[u].y >> 16) ? 1u : 0u);
+					const uint64_t v = ((uint64_t)q[u].w << 32) | q[u].z;
+					const uint32_t leaf = ldict[inl ? (uint32_t)(v >> (12u * cnt)) & 0xFFFu : 0u];
+					e[u] = !act[u] ? 0u : (inl ? leaf : q[u].x);
+				}
+			} else {
 				/* one 16-byte gather: the /16's inline run node (tables.h) */
 				uint4 q[Q];
 				uint4 tq[TUN ? Q : 1];
@@ -2361,6 +2523,70 @@ __global__ __launch_bounds__(NT, MINW) void k_classify_x4(cgpu_snapshot s, cls_a
 				for (int u = 0; u < Q; u++)
 					if ((e[u] >> LPMC_KIND_SHIFT) == ARR)
 						e[u] = s.ipc4c.nodes[(size_t)(e[u] & LPMC_OFF_MASK) * 4u + (bswap32(ad[u]) & 255u)];
+				if constexpr (QX) {
+					/* the first 32 bytes of every tuple's node in flight
+					 * together: all the run starts of a node (lpmc_search:
+					 * words 0..4 at most) and the leaves of a 16- or 32-byte
+					 * one.  A 64-byte node's leaf beyond them is then ONE
+					 * word, gathered for the Q tuples together behind a
+					 * wave-uniform branch (most quads have none); its whole
+					 * second half for four tuples does not fit the register
+					 * file.  A tuple without a node reads x16's slot 0, a
+					 * 16-byte node its only 16 bytes again (`nodes` may be
+					 * empty) */
+					bool grpn[Q], far[Q], anyn = false, anyf = false;
+					uint32_t kind[Q], idx[Q];
+#pragma unroll
+					for (int u = 0; u < Q; u++) {
+						grpn[u] = (e[u] & DIR_TAG_MASK) == DIR_TAG_GROUP;
+						kind[u] = grpn[u] ? (e[u] >> LPMC_KIND_SHIFT) & 3u : 0u;
+						anyn |= grpn[u];
+					}
+					if (__ballot(anyn)) {
+						uint4 q[Q][2];
+#pragma unroll
+						for (int u = 0; u < Q; u++) {
+							const uint4 *nd = grpn[u] ? reinterpret_cast<const uint4 *>(s.ipc4c.nodes) +
+											    (e[u] & LPMC_OFF_MASK)
+										  : reinterpret_cast<const uint4 *>(s.ipc4c.x16);
+							q[u][0] = nd[0];
+							q[u][1] = nd[kind[u] ? 1 : 0];
+						}
+#pragma unroll
+						for (int u = 0; u < Q; u++) {
+							/* lpmc_search, its leaf taken from words 1..7 */
+							const uint32_t w[8] = {q[u][0].x, q[u][0].y, q[u][0].z, q[u][0].w,
+									       q[u][1].x, q[u][1].y, q[u][1].z, q[u][1].w};
+							const uint32_t h = bswap32(ad[u]);
+							const uint32_t x = (fw[u] & F_LVL8) ? (h & 255u) : (h & 0xFFFFu);
+							const uint32_t nb = kind[u] == 0 ? 1u : (kind[u] == 1 ? 2u : 5u);
+							uint32_t cnt = 0;
+#pragma unroll
+							for (uint32_t i = 0; i < 5; i++)
+								if (i < nb)
+									cnt += (x >= (w[i] & 0xFFFFu) ? 1u : 0u) + (x >= (w[i] >> 16) ? 1u : 0u);
+							idx[u] = nb + cnt;
+							uint32_t r = w[1];
+#pragma unroll
+							for (uint32_t j = 2; j < 8; j++)
+								r = j == idx[u] ? w[j] : r;
+							far[u] = grpn[u] && idx[u] >= 8u;
+							anyf |= far[u];
+							if (grpn[u] && !far[u])
+								e[u] = r;
+						}
+						if (__ballot(anyf)) {
+							uint32_t r[Q];
+#pragma unroll
+							for (int u = 0; u < Q; u++)
+								r[u] = *(far[u] ? s.ipc4c.nodes + (size_t)(e[u] & LPMC_OFF_MASK) * 4u + idx[u]
+										: s.ipc4c.x16);
+#pragma unroll
+							for (int u = 0; u < Q; u++)
+								e[u] = far[u] ? r[u] : e[u];
+						}
+					}
+				} else {
 				/* the first 32 bytes of every node in flight together; the
 				 * rare 64-byte node reads its second half one tuple at a time */
 				uint4 q[Q][2];
@@ -2391,14 +2617,39 @@ __global__ __launch_bounds__(NT, MINW) void k_classify_x4(cgpu_snapshot s, cls_a
 					e[u] = lpmc_search(q[u][0], q[u][1], q2, q3, kind,
 							   (fw[u] & F_LVL8) ? (h & 255u) : (h & 0xFFFFu));
 				}
+				}
 			}
 		}
 		/* identity (bpf_lxc.c:488-496 / bpf_netdev.c:374-404) */
 		uint32_t id[QA];
 		uint32_t tv[TUN ? QA : 1];
+		/* QX: the label words of the leaves that index `vals` (labels >= 2^30),
+		 * the Q loads together behind a wave-uniform branch; another tuple
+		 * reads x16's word 0 (`vals` may be empty) */
+		uint32_t lv[QX ? Q : 1];
+		if constexpr (QX) {
+			bool anyi = false;
+#pragma unroll
+			for (int u = 0; u < Q; u++)
+				anyi |= (e[u] & DIR_TAG_MASK) == DIR_TAG_INDIRECT;
+#pragma unroll
+			for (int u = 0; u < Q; u++)
+				lv[u] = 0u;
+			if (__ballot(anyi)) {
+#pragma unroll
+				for (int u = 0; u < Q; u++)
+					lv[u] = *((e[u] & DIR_TAG_MASK) == DIR_TAG_INDIRECT
+							  ? s.ipc4c.vals + (e[u] & DIR_PAYLOAD_MASK)
+							  : s.ipc4c.x16);
+			}
+		}
 #pragma unroll
 		for (int u = 0; u < Q; u++) {
-			const uint32_t label = entry_label(V6 ? s.ipc6.vals : s.ipc4c.vals, e[u]);
+			uint32_t label;
+			if constexpr (QX)
+				label = (e[u] & DIR_TAG_MASK) == DIR_TAG_INDIRECT ? lv[u] : e[u] & DIR_PAYLOAD_MASK;
+			else
+				label = entry_label(V6 ? s.ipc6.vals : s.ipc4c.vals, e[u]);
 			if constexpr (TUN) /* bpf_lxc.c:488-491 / :177-180: sec_label != 0 */
 				tv[u] = (twant[u] && e[u] && label) ? entry_label(V6 ? ta.t.t6.vals : ta.t.t4.vals, te[u]) : 0u;
 			/* v6: ipv6_match_prefix_64(daddr, ROUTER_IP), bpf/lib/ipv6.h:166-175
@@ -2435,20 +2686,48 @@ __global__ __launch_bounds__(NT, MINW) void k_classify_x4(cgpu_snapshot s, cls_a
 			z[u] = 0;
 			st[u] = 0;
 			grp[u] = make_uint4(0, 0, POL_CTR_EMPTY, 0);
+			if constexpr (QX) /* (read, and dropped, by the quad-wide stages) */
+				bk[u] = need[u] = 0u;
 			if ((fw[u] & (F_OK | F_GATED | F_LBDROP)) == F_OK) {
 				bk[u] = pg_hash(id[u], ep[u] | (hi4[u] >> 24) << 16) & s.pg.mask;
 				grp[u] = s.pg.slots[DIAG_P2(bk[u])];
 			}
 		}
+		if constexpr (QX) {
+			bool act[Q];
+			uint32_t ed[Q];
+#pragma unroll
+			for (int u = 0; u < Q; u++) {
+				act[u] = (fw[u] & (F_OK | F_GATED | F_LBDROP)) == F_OK;
+				ed[u] = ep[u] | (hi4[u] >> 24) << 16;
+			}
+			pg_resolve_q<Q>(s.pg, grp, bk, id, ed, act);
+		}
 #pragma unroll
 		for (int u = 0; u < Q; u++) {
 			if ((fw[u] & (F_OK | F_GATED | F_LBDROP)) != F_OK)
 				continue;
-			grp[u] = pg_resolve(s.pg, grp[u], bk[u], id[u], ep[u] | (hi4[u] >> 24) << 16);
+			if constexpr (!QX)
+				grp[u] = pg_resolve(s.pg, grp[u], bk[u], id[u], ep[u] | (hi4[u] >> 24) << 16);
 			const uint32_t bl = pg_bloom(hi4[u] & 0xFFFFu, (hi4[u] >> 16) & 0xFFu);
 			need[u] = !(fw[u] & F_FRAG) && (grp[u].w & bl) == bl;
 		}
 		/* probe 1: exact {id, dport, proto, dir} (policy.h:61-72) */
+		if constexpr (QX) {
+			/* the Q home slots together (a tuple without the probe reads
+			 * slot 0), then the hop slots in quad-wide rounds */
+			bool w1[Q];
+#pragma unroll
+			for (int u = 0; u < Q; u++) {
+				w1[u] = (fw[u] & (F_OK | F_GATED | F_LBDROP)) == F_OK && need[u];
+				bk[u] = w1[u] ? pol_hash(id[u], hi4[u], ep[u]) & pmask : 0u;
+				sl[u] = ptab[DIAG_P1(bk[u])];
+			}
+			pol_resolve_q<Q>(s.pol, sl, bk, id, hi4, ep, w1, ctr, z);
+#pragma unroll
+			for (int u = 0; u < Q; u++)
+				st[u] = w1[u] ? 1u : st[u];
+		} else {
 #pragma unroll
 		for (int u = 0; u < Q; u++)
 			if ((fw[u] & (F_OK | F_GATED | F_LBDROP)) == F_OK && need[u]) {
@@ -2461,6 +2740,7 @@ __global__ __launch_bounds__(NT, MINW) void k_classify_x4(cgpu_snapshot s, cls_a
 				ctr[u] = pol_resolve1(s.pol, sl[u], bk[u], id[u], hi4[u], ep[u], &z[u]);
 				st[u] = 1;
 			}
+		}
 		/* probe 2: L3-only {id, 0, 0, dir} (policy.h:74-83), from the group */
 #pragma unroll
 		for (int u = 0; u < Q; u++)
@@ -2472,6 +2752,27 @@ __global__ __launch_bounds__(NT, MINW) void k_classify_x4(cgpu_snapshot s, cls_a
 				}
 			}
 		/* probe 3: identity-wildcard L4 {0, dport, proto, dir} (policy.h:85-96) */
+		if constexpr (QX) {
+			/* as probe 1, behind a wave-uniform branch */
+			bool w3[Q], any3 = false;
+#pragma unroll
+			for (int u = 0; u < Q; u++) {
+				w3[u] = (fw[u] & (F_OK | F_GATED | F_LBDROP | F_FRAG)) == F_OK && ctr[u] < 0;
+				any3 |= w3[u];
+			}
+			if (__ballot(any3)) {
+				const uint32_t id0[Q] = {0u, 0u, 0u, 0u};
+#pragma unroll
+				for (int u = 0; u < Q; u++) {
+					bk[u] = w3[u] ? pol_hash(0u, hi4[u], ep[u]) & pmask : 0u;
+					sl[u] = ptab[bk[u]];
+				}
+				pol_resolve_q<Q>(s.pol, sl, bk, id0, hi4, ep, w3, ctr, z);
+#pragma unroll
+				for (int u = 0; u < Q; u++)
+					st[u] = w3[u] ? 3u : st[u];
+			}
+		} else {
 #pragma unroll
 		for (int u = 0; u < Q; u++)
 			if ((fw[u] & (F_OK | F_GATED | F_LBDROP | F_FRAG)) == F_OK && ctr[u] < 0) {
@@ -2484,6 +2785,7 @@ __global__ __launch_bounds__(NT, MINW) void k_classify_x4(cgpu_snapshot s, cls_a
 				ctr[u] = pol_resolve1(s.pol, sl[u], bk[u], 0u, hi4[u], ep[u], &z[u]);
 				st[u] = 3;
 			}
+		}
 		/* counters, outputs, metrics */
 		int32_t v[QA];
 		uint64_t *metg = a.delta + 2ull * s.n_ctr_slots;

@@ -8,7 +8,9 @@ product library: these builds drop work and give wrong counters).
 Each variant is cilium_amd/csrc compiled with extra -D flags into
 tools/_diag/libcgpu_<name>.so; `run` loads each in turn into the Engine
 (cilium_amd._abi's loader is pointed at it), commits the workload's tables and
-times 10 launches of its 64M-tuple batch with HIP events.""" 
+times 10 launches (CGPU_AB_LAUNCHES) of its 64M-tuple batch with HIP events.
+A name that is no variant loads tools/_diag/libcgpu_<name>.so as it is, for
+instance the parent commit's library next to `product`."""
 import ctypes as C
 import json
 import os
@@ -75,6 +77,10 @@ VARIANTS = {"product": (), "no_cold_atomics": ("CGPU_DIAG_NO_COLD",),
             # LB frontend slots per frontend (hopscotch, round 6): 2 = 32 MiB at config 5
             "lb_fe4": ("CGPU_LB_SLOTS_PER_FE=4",), "lb_fe8": ("CGPU_LB_SLOTS_PER_FE=8",),
             "lb_fe16": ("CGPU_LB_SLOTS_PER_FE=16",),
+            # (the plain x4 kernel gathering probe 3's home slot with probe 1's, one
+            # round trip less for a quad that reaches probe 3, measured 1.658-1.665
+            # -> 1.665-1.673 ms: profiles/x4_stages/ab_x4_stages_spec_p3.log; the
+            # macro left the tree with the result)
             # the cascade kernel's tuples per lane (product 2, r6_l; sep_q2 was
             # the same define on the stages-apart source)
             "xdp_q4": ("CGPU_XDP_Q=4",), "no_defer_cold": ("CGPU_X4_DEFER_COLD=0",), "no_ct_dflt": ("CGPU_CT_DFLT=0",),
@@ -288,15 +294,17 @@ def run(names):
         if os.environ.get("CGPU_AB_REBALANCE"):  # as bench.py after its warmup
             torch.cuda.synchronize()
             e.counters_rebalance()
-        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(10)]
+        reps = int(os.environ.get("CGPU_AB_LAUNCHES", "10"))
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
         for a, b in ev:
             a.record()
             launch(e)
             b.record()
         torch.cuda.synchronize()
         ms = sorted(a.elapsed_time(b) for a, b in ev)
-        print(json.dumps({"variant": name, "median_ms": round(ms[5], 4), "min_ms": round(ms[0], 4),
-                          "gpps": round(n / ms[5] / 1e6, 2)}), flush=True)
+        med = ms[reps // 2]
+        print(json.dumps({"variant": name, "median_ms": round(med, 4), "min_ms": round(ms[0], 4),
+                          "gpps": round(n / med / 1e6, 2), "launches": reps}), flush=True)
         e.close()
 
 
