@@ -78,6 +78,20 @@ class Rnat6Out(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("saddr", "sport", "applied")]
 
 
+class FwdParams(C.Structure):
+    _fields_ = [("mode", C.c_uint32), ("flags", C.c_uint32), ("ipv4_mask", C.c_uint32),
+                ("host_ifindex", C.c_uint32), ("encap_ifindex", C.c_uint32),
+                ("reserved", C.c_uint32 * 3)]
+
+
+class FwdIn(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("daddr", "verdict", "tunnel", "flags", "ttl")]
+
+
+class FwdOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("action", "ret", "ifindex", "arg")]
+
+
 class Frames(C.Structure):
     _fields_ = [("data", C.c_void_p), ("len", C.c_void_p), ("flags", C.c_void_p),
                 ("ep", C.c_void_p), ("stride", C.c_uint32), ("reserved", C.c_uint32)]
@@ -126,6 +140,16 @@ PROTOS = {
     "cgpu_endpoint_update": (i32, [vp, vp, u64]),
     "cgpu_endpoint_delete": (i32, [vp, vp]),
     "cgpu_endpoint_lookup": (i32, [vp, vp]),
+    "cgpu_endpoint_update_info": (i32, [vp, vp, vp, u64]),
+    "cgpu_endpoint_lookup_info": (i32, [vp, vp, vp]),
+    "cgpu_tunnel_update": (i32, [vp, vp, vp, u64]),
+    "cgpu_tunnel_delete": (i32, [vp, vp]),
+    "cgpu_tunnel_lookup": (i32, [vp, vp, vp]),
+    "cgpu_tunnel_get_next_key": (i32, [vp, vp, vp]),
+    "cgpu_tunnel_count": (sz, [vp]),
+    "cgpu_forward_v4": (i32, [vp, C.POINTER(FwdParams), C.POINTER(FwdIn), sz, C.POINTER(FwdOut), vp]),
+    "cgpu_forward_v6": (i32, [vp, C.POINTER(FwdParams), C.POINTER(FwdIn), sz, C.POINTER(FwdOut), vp]),
+    "cgpu_forward_table_bytes": (i32, [vp, vp]),
     "cgpu_lb4_update": (i32, [vp, vp, vp, u64]),
     "cgpu_lb4_update_batch": (i32, [vp, vp, vp, sz, u64]),
     "cgpu_lb4_delete": (i32, [vp, vp]),

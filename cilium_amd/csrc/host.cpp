@@ -1904,6 +1904,7 @@ struct BuildState {
 	PolBuild pol;
 	PgBuild pg;
 	uint64_t sum[G_N] = {};
+	uint64_t sum_fwd = 0; /* forwarding tables' content (0: not built) */
 };
 
 /* One conntrack map (tables.h ct_table layout; CtK4 / CtK6 slots in
@@ -1977,6 +1978,13 @@ struct cgpu_ctx {
 	std::set<std::array<uint8_t, 8>> fix4;
 	std::set<std::array<uint8_t, 20>> fix6;
 	std::set<std::array<uint8_t, 20>> lxc;
+	/* the values of cilium_lxc that are not all-zero (cgpu_endpoint_update_info)
+	 * and cilium_tunnel_map: read by the forwarding step alone, whose device
+	 * tables (tables.h fwd_tables) a commit builds after a change of either map
+	 * or of the endpoint keys, and only while one of the two holds something */
+	std::map<std::array<uint8_t, 20>, cgpu_endpoint_info> lxc_info;
+	std::map<std::array<uint8_t, 20>, std::array<uint8_t, 20>> tun;
+	bool fwd_dirty = false, fwd_built = false;
 	/* cilium_lb4_services, keyed address << 32 | dport << 16 | slave so that
 	 * a frontend's entries are adjacent */
 	std::map<uint64_t, cgpu_lb4_service> lb;
@@ -2064,7 +2072,9 @@ struct Epoch {
 	uint64_t id = 0;
 	cgpu_snapshot snap{};
 	ipc_tun tun{}; /* into bufs[G_IPC]; t4.d16 == NULL without cgpu_config.ipcache_tunnel */
+	fwd_tables fwd{}; /* into fwdbuf; e4 == NULL: not built */
 	DevBufP bufs[G_N];
+	DevBufP fwdbuf;   /* outside the verified groups: cgpu_table_bytes / _checksum / _verify leave it out */
 	hipEvent_t ready = nullptr;
 	std::mutex mu;
 	std::vector<std::pair<hipStream_t, hipEvent_t>> used;
@@ -2986,8 +2996,130 @@ CGPU_EXPORT int cgpu_endpoint_update(cgpu_ctx *c, const cgpu_endpoint_key *key, 
 	if (!exists && flags == CGPU_EXIST) return fail(-ENOENT, "missing");
 	if (!exists && c->lxc.size() >= c->cfg.endpoints_max) return fail(-E2BIG, "endpoint map full");
 	c->lxc.insert(k);
+	c->lxc_info.erase(k); /* an update with an all-zero value */
 	c->dirty |= 1u << G_EP;
+	c->fwd_dirty = true;
 	return 0;
+}
+
+CGPU_EXPORT int cgpu_endpoint_update_info(cgpu_ctx *c, const cgpu_endpoint_key *key, const cgpu_endpoint_info *info,
+					  uint64_t flags)
+{
+	if (!c || !key || !info)
+		return fail(-EINVAL, "null argument");
+	if (int r = check_flags(flags))
+		return r;
+	std::array<uint8_t, 20> k;
+	memcpy(k.data(), key, 20);
+	static const cgpu_endpoint_info zero{};
+	std::lock_guard<std::mutex> g(c->mu);
+	const bool exists = c->lxc.count(k);
+	if (exists && flags == CGPU_NOEXIST) return fail(-EEXIST, "exists");
+	if (!exists && flags == CGPU_EXIST) return fail(-ENOENT, "missing");
+	if (!exists && c->lxc.size() >= c->cfg.endpoints_max) return fail(-E2BIG, "endpoint map full");
+	if (!exists) {
+		c->lxc.insert(k);
+		c->dirty |= 1u << G_EP;
+	}
+	if (memcmp(info, &zero, sizeof(zero)))
+		c->lxc_info[k] = *info;
+	else
+		c->lxc_info.erase(k);
+	c->fwd_dirty = true;
+	return 0;
+}
+
+CGPU_EXPORT int cgpu_endpoint_lookup_info(cgpu_ctx *c, const cgpu_endpoint_key *key, cgpu_endpoint_info *out)
+{
+	if (!c || !key || !out)
+		return fail(-EINVAL, "null argument");
+	std::array<uint8_t, 20> k;
+	memcpy(k.data(), key, 20);
+	std::lock_guard<std::mutex> g(c->mu);
+	if (!c->lxc.count(k))
+		return -ENOENT;
+	auto it = c->lxc_info.find(k);
+	*out = it == c->lxc_info.end() ? cgpu_endpoint_info{} : it->second;
+	return 0;
+}
+
+/* ---- cilium_tunnel_map (bpf/lib/maps.h:92-101; the agent: pkg/maps/tunnel/
+ * tunnel.go): a hash map, whole-key compare ---- */
+CGPU_EXPORT int cgpu_tunnel_update(cgpu_ctx *c, const cgpu_endpoint_key *key, const cgpu_endpoint_key *val,
+				   uint64_t flags)
+{
+	if (!c || !key || !val)
+		return fail(-EINVAL, "null argument");
+	if (int r = check_flags(flags))
+		return r;
+	std::array<uint8_t, 20> k, v;
+	memcpy(k.data(), key, 20);
+	memcpy(v.data(), val, 20);
+	std::lock_guard<std::mutex> g(c->mu);
+	auto it = c->tun.find(k);
+	if (it == c->tun.end()) {
+		if (flags == CGPU_EXIST)
+			return fail(-ENOENT, "tunnel key not present");
+		if (c->tun.size() >= CGPU_TUNNEL_MAP_SIZE)
+			return fail(-E2BIG, "tunnel map full (%u)", CGPU_TUNNEL_MAP_SIZE);
+		c->tun.emplace(k, v);
+	} else {
+		if (flags == CGPU_NOEXIST)
+			return fail(-EEXIST, "tunnel key exists");
+		it->second = v;
+	}
+	c->fwd_dirty = true;
+	return 0;
+}
+
+CGPU_EXPORT int cgpu_tunnel_delete(cgpu_ctx *c, const cgpu_endpoint_key *key)
+{
+	if (!c || !key)
+		return fail(-EINVAL, "null argument");
+	std::array<uint8_t, 20> k;
+	memcpy(k.data(), key, 20);
+	std::lock_guard<std::mutex> g(c->mu);
+	if (!c->tun.erase(k))
+		return -ENOENT;
+	c->fwd_dirty = true;
+	return 0;
+}
+
+CGPU_EXPORT int cgpu_tunnel_lookup(cgpu_ctx *c, const cgpu_endpoint_key *key, cgpu_endpoint_key *out)
+{
+	if (!c || !key || !out)
+		return fail(-EINVAL, "null argument");
+	std::array<uint8_t, 20> k;
+	memcpy(k.data(), key, 20);
+	std::lock_guard<std::mutex> g(c->mu);
+	auto it = c->tun.find(k);
+	if (it == c->tun.end())
+		return -ENOENT;
+	memcpy(out, it->second.data(), 20);
+	return 0;
+}
+
+CGPU_EXPORT int cgpu_tunnel_get_next_key(cgpu_ctx *c, const cgpu_endpoint_key *key, cgpu_endpoint_key *next)
+{
+	if (!c || !next)
+		return fail(-EINVAL, "null argument");
+	std::array<uint8_t, 20> k{};
+	if (key)
+		memcpy(k.data(), key, 20);
+	std::lock_guard<std::mutex> g(c->mu);
+	auto it = key ? c->tun.upper_bound(k) : c->tun.begin();
+	if (it == c->tun.end())
+		return -ENOENT;
+	memcpy(next, it->first.data(), 20);
+	return 0;
+}
+
+CGPU_EXPORT size_t cgpu_tunnel_count(cgpu_ctx *c)
+{
+	if (!c)
+		return 0;
+	std::lock_guard<std::mutex> g(c->mu);
+	return c->tun.size();
 }
 
 CGPU_EXPORT int cgpu_endpoint_delete(cgpu_ctx *c, const cgpu_endpoint_key *key)
@@ -2999,7 +3131,9 @@ CGPU_EXPORT int cgpu_endpoint_delete(cgpu_ctx *c, const cgpu_endpoint_key *key)
 	std::lock_guard<std::mutex> g(c->mu);
 	if (!c->lxc.erase(k))
 		return -ENOENT;
+	c->lxc_info.erase(k);
 	c->dirty |= 1u << G_EP;
+	c->fwd_dirty = true;
 	return 0;
 }
 
@@ -3451,6 +3585,11 @@ struct CommitIn {
 	Lb6In lb6;
 	std::vector<std::pair<uint32_t, cgpu_lxc_info>> lxcinfo;
 	uint64_t sum_ipc = 0, sum_pol = 0, sum_slots = 0;
+	/* forwarding tables: rebuilt (fwd), from every endpoint with its value and
+	 * the tunnel map; both empty = the tables go away */
+	bool fwd = false;
+	std::vector<std::pair<std::array<uint8_t, 20>, cgpu_endpoint_info>> fwd_ep;
+	std::vector<std::pair<std::array<uint8_t, 20>, std::array<uint8_t, 20>>> fwd_tun;
 };
 
 
@@ -3654,6 +3793,20 @@ static void capture(cgpu_ctx *c, CommitIn &in, const BuildState &b)
 	in.sum_ipc = c->sum_ipc;
 	in.sum_pol = c->sum_pol;
 	in.sum_slots = c->sum_slots;
+	if (c->fwd_dirty) {
+		const bool need = !c->lxc_info.empty() || !c->tun.empty();
+		in.fwd = need || c->fwd_built;
+		if (need) {
+			in.fwd_ep.reserve(c->lxc.size());
+			for (auto &k : c->lxc) {
+				auto it = c->lxc_info.find(k);
+				in.fwd_ep.push_back({k, it == c->lxc_info.end() ? cgpu_endpoint_info{} : it->second});
+			}
+			in.fwd_tun.assign(c->tun.begin(), c->tun.end());
+		}
+		c->fwd_built = need;
+		c->fwd_dirty = false;
+	}
 	c->dirty = 0;
 	in.id = ++c->captured;
 }
@@ -3662,6 +3815,8 @@ static void capture(cgpu_ctx *c, CommitIn &in, const BuildState &b)
 static void uncapture(cgpu_ctx *c, const CommitIn &in)
 {
 	c->dirty |= in.dirty;
+	if (in.fwd)
+		c->fwd_dirty = c->fwd_built = true;
 	if (in.dirty & (1u << G_IPC)) {
 		c->ipc_full = true;
 		c->ipc_changes.clear();
@@ -4135,6 +4290,102 @@ static int commit_lxc(cgpu_ctx *c, CommitIn &in, cgpu_snapshot &s, DevBufP &buf)
 	return 0;
 }
 
+/* rows of W words into a single-slot neighbourhood hash (tables.h fwd_tables):
+ * first fit within POL_HOP slots of the home slot, the table doubled until
+ * every row fits; word T of a slot is FWD_USED | hop << 24 (0 in `rows`) */
+template <size_t W, size_t T, class H>
+static void build_hop(const std::vector<std::array<uint32_t, W>> &rows, H home_of,
+		      std::vector<std::array<uint32_t, W>> &out, uint32_t &mask)
+{
+	uint32_t nb = next_pow2(std::max<uint64_t>(64, 2 * rows.size()));
+	for (;; nb *= 2) {
+		out.assign(nb, std::array<uint32_t, W>{});
+		mask = nb - 1;
+		bool ok = true;
+		for (auto &r : rows) {
+			const uint32_t home = home_of(r) & mask;
+			uint32_t d = 0;
+			while (d < POL_HOP && (out[(home + d) & mask][T] & FWD_USED))
+				d++;
+			if (d == POL_HOP) {
+				ok = false;
+				break;
+			}
+			auto &sl = out[(home + d) & mask];
+			const uint32_t hop = sl[T] & ~POL_CTR_MASK;
+			sl = r;
+			sl[T] = hop | FWD_USED;
+			out[home][T] |= 1u << (POL_HOP_SHIFT + d);
+		}
+		if (ok)
+			return;
+	}
+}
+
+/* the forwarding tables (tables.h fwd_tables) from every endpoint with its
+ * value and the tunnel map; nothing to build: the snapshot has none */
+static int commit_fwd(cgpu_ctx *c, CommitIn &in, Epoch &e)
+{
+	e.fwdbuf.reset();
+	e.fwd = fwd_tables{};
+	c->b.sum_fwd = 0;
+	if (in.fwd_ep.empty() && in.fwd_tun.empty())
+		return 0;
+	std::vector<std::array<uint32_t, 4>> r4, t4, o_e4, o_t4;
+	std::vector<std::array<uint32_t, 8>> r6, t6, o_e6, o_t6;
+	static const cgpu_endpoint_info zero{};
+	uint64_t sum = 0;
+	/* only keys the programs build can match (lookup_ip4_endpoint /
+	 * lookup_ip6_endpoint, eps.h:13-45; the tunnel keys of bpf_lxc.c:610-611,
+	 * :306-312): zero pad bytes, the family's tag, zero pad words */
+	auto words = [](const std::array<uint8_t, 20> &k, uint32_t (&w)[4]) {
+		const cgpu_endpoint_key *ek = (const cgpu_endpoint_key *)k.data();
+		memcpy(w, ek->ip, 16);
+		return (ek->pad4 || ek->pad5) ? 0u : (uint32_t)ek->family;
+	};
+	for (auto &kv : in.fwd_ep) {
+		const cgpu_endpoint_info &v = kv.second;
+		if (memcmp(&v, &zero, sizeof(zero)))
+			sum += fnv(fnv(37, kv.first.data(), 20), &v, sizeof(v));
+		uint32_t w[4];
+		const uint32_t fam = words(kv.first, w);
+		const uint32_t val = (uint32_t)v.lxc_id | ((v.flags & CGPU_ENDPOINT_F_HOST) ? FWD_HOST_BIT : 0u);
+		if (fam == 1 && !w[1] && !w[2] && !w[3])
+			r4.push_back({w[0], v.ifindex, val, 0});
+		else if (fam == 2)
+			r6.push_back({w[0], w[1], w[2], w[3], v.ifindex, val, 0, 0});
+	}
+	for (auto &kv : in.fwd_tun) {
+		sum += fnv(fnv(41, kv.first.data(), 20), kv.second.data(), 20);
+		uint32_t w[4], ip4;
+		const uint32_t fam = words(kv.first, w);
+		memcpy(&ip4, kv.second.data(), 4); /* tunnel->ip4 is all the datapath reads */
+		if (fam == 1 && !w[1] && !w[2] && !w[3])
+			t4.push_back({w[0], ip4, 0, 0});
+		else if (fam == 2 && !w[3])
+			t6.push_back({w[0], w[1], w[2], ip4, 0, 0, 0, 0});
+	}
+	fwd_tables f{};
+	build_hop<4, 3>(r4, [](const std::array<uint32_t, 4> &r) { return fwd_hash4(r[0]); }, o_e4, f.e4_mask);
+	build_hop<4, 3>(t4, [](const std::array<uint32_t, 4> &r) { return fwd_hash4(r[0]); }, o_t4, f.t4_mask);
+	build_hop<8, 6>(r6, [](const std::array<uint32_t, 8> &r) { return fold6(r[0], r[1], r[2], r[3]); }, o_e6,
+			f.e6_mask);
+	build_hop<8, 6>(t6, [](const std::array<uint32_t, 8> &r) { return fold6(r[0], r[1], r[2], 0u); }, o_t6,
+			f.t6_mask);
+	Arena ar;
+	const size_t a_e4 = ar.add(o_e4.data(), o_e4.size() * 16), a_e6 = ar.add(o_e6.data(), o_e6.size() * 32);
+	const size_t a_t4 = ar.add(o_t4.data(), o_t4.size() * 16), a_t6 = ar.add(o_t6.data(), o_t6.size() * 32);
+	if (int r = upload(c, ar, e.fwdbuf, G_N)) /* G_N: summed into the scratch word, not a verified group */
+		return r;
+	f.e4 = at<uint4>(e.fwdbuf, a_e4);
+	f.e6 = at<uint4>(e.fwdbuf, a_e6);
+	f.t4 = at<uint4>(e.fwdbuf, a_t4);
+	f.t6 = at<uint4>(e.fwdbuf, a_t6);
+	e.fwd = f;
+	c->b.sum_fwd = sum;
+	return 0;
+}
+
 /* counter slots whose entry was (re)written: their totals restart from the
  * supplied packets/bytes (kernel htab update replaces the value); the newest
  * write of a slot wins */
@@ -4207,6 +4458,8 @@ static int commit_locked(cgpu_ctx *c, uint64_t *epoch_out)
 	if (prev) {
 		e->snap = prev->snap;
 		e->tun = prev->tun;
+		e->fwd = prev->fwd;
+		e->fwdbuf = prev->fwdbuf;
 		for (int k = 0; k < G_N; k++)
 			e->bufs[k] = prev->bufs[k];
 	}
@@ -4226,6 +4479,8 @@ static int commit_locked(cgpu_ctx *c, uint64_t *epoch_out)
 		}
 	if (!rc && (in.dirty & (1u << G_IPC)))
 		e->tun = c->b.tun;
+	if (!rc && in.fwd)
+		rc = commit_fwd(c, in, *e);
 	if (!rc)
 		rc = commit_inits(c, in);
 	hipError_t he = hipSuccess;
@@ -4281,6 +4536,7 @@ static int commit_locked(cgpu_ctx *c, uint64_t *epoch_out)
 	uint64_t sum = 0;
 	for (int k = 0; k < G_N; k++)
 		sum += c->b.sum[k];
+	sum += c->b.sum_fwd;
 	{
 		std::lock_guard<std::mutex> g(c->retire_mu);
 		c->alive.insert(e->id);
@@ -4869,6 +5125,86 @@ CGPU_EXPORT int cgpu_ipcache_lookup_v6(cgpu_ctx *c, const uint8_t *addr16, size_
 				       uint32_t *sec_label, uint32_t *tunnel, void *stream)
 {
 	return ipcache_lookup_batch(c, addr16, n, 1, found, sec_label, tunnel, stream);
+}
+
+/* the forwarding step (cgpu.h cgpu_forward_v4 / _v6): the parameter block is
+ * judged before the context, so a malformed call is -EINVAL everywhere */
+static int forward_batch(cgpu_ctx *c, const cgpu_fwd_params *p, const cgpu_fwd_in *in, size_t n,
+			 const cgpu_fwd_out *out, int v6, void *stream)
+{
+	if (!c || !p || !in || !out)
+		return fail(-EINVAL, "null argument");
+	if (p->mode != CGPU_FWD_LXC && p->mode != CGPU_FWD_NETDEV)
+		return fail(-EINVAL, "bad forwarding mode %u", p->mode);
+	if (p->flags & ~CGPU_FWD_ENCAP)
+		return fail(-EINVAL, "unknown forwarding flags 0x%x", p->flags);
+	if (p->reserved[0] || p->reserved[1] || p->reserved[2])
+		return fail(-EINVAL, "cgpu_fwd_params.reserved must be 0");
+	Pinned P;
+	if (int r = pin(c, stream, P))
+		return r;
+	if (n && (!in->daddr || !out->action))
+		return fail(-EINVAL, "null daddr or action column");
+	if (n && p->mode == CGPU_FWD_LXC && (!in->verdict || !in->flags))
+		return fail(-EINVAL, "CGPU_FWD_LXC needs the verdict and flags columns");
+	if (!v6 && ((uintptr_t)in->daddr & 3u))
+		return fail(-EINVAL, "IPv4 address column not 4-byte aligned");
+	if (((uintptr_t)in->verdict | (uintptr_t)in->tunnel | (uintptr_t)out->ret | (uintptr_t)out->ifindex |
+	     (uintptr_t)out->arg) & 3u)
+		return fail(-EINVAL, "4-byte column not 4-byte aligned");
+	if (!n)
+		return 0;
+	fwd_args a{};
+	a.daddr = in->daddr;
+	a.verdict = in->verdict;
+	a.tunnel = in->tunnel;
+	a.flags = in->flags;
+	a.ttl = in->ttl;
+	a.action = out->action;
+	a.ret = out->ret;
+	a.ifindex = out->ifindex;
+	a.arg = out->arg;
+	a.n = n;
+	a.mode = p->mode;
+	a.encap = p->flags & CGPU_FWD_ENCAP;
+	a.ipv4_mask = p->ipv4_mask;
+	a.host_ifindex = p->host_ifindex;
+	a.encap_ifindex = p->encap_ifindex;
+	a.v6 = v6;
+	HIP_OR_EIO(launch_forward(P.snap(), P.ep->fwd, a, (hipStream_t)stream));
+	return 0;
+}
+
+CGPU_EXPORT int cgpu_forward_v4(cgpu_ctx *c, const cgpu_fwd_params *p, const cgpu_fwd_in *in, size_t n,
+				const cgpu_fwd_out *out, void *stream)
+{
+	return forward_batch(c, p, in, n, out, 0, stream);
+}
+
+CGPU_EXPORT int cgpu_forward_v6(cgpu_ctx *c, const cgpu_fwd_params *p, const cgpu_fwd_in *in, size_t n,
+				const cgpu_fwd_out *out, void *stream)
+{
+	return forward_batch(c, p, in, n, out, 1, stream);
+}
+
+CGPU_EXPORT int cgpu_forward_table_bytes(cgpu_ctx *c, uint64_t *out)
+{
+	if (!c || !out)
+		return fail(-EINVAL, "null argument");
+	std::shared_ptr<Epoch> ep;
+	{
+		std::lock_guard<std::mutex> g(c->pub_mu);
+		ep = c->cur;
+	}
+	if (!ep)
+		return fail(-ENOENT, "nothing committed");
+	const fwd_tables &f = ep->fwd;
+	const bool built = f.e4 != nullptr;
+	out[0] = built ? (f.e4_mask + 1ull) * 16u : 0;
+	out[1] = built ? (f.e6_mask + 1ull) * 32u : 0;
+	out[2] = built ? (f.t4_mask + 1ull) * 16u : 0;
+	out[3] = built ? (f.t6_mask + 1ull) * 32u : 0;
+	return 0;
 }
 
 /* ---- host-resident batches (host or device pointers) ----
@@ -6839,7 +7175,11 @@ CGPU_EXPORT int cgpu_classify_v6_ct_tun(cgpu_ctx *c, const cgpu_tuples_v6_ct *t,
  * hash of everything before it. */
 enum { MIR_IPC = 1, MIR_POL, MIR_CIDR, MIR_EP, MIR_LB4, MIR_LB6, MIR_LXC, MIR_REV, MIR_CT4, MIR_CT6,
        MIR_RN4, MIR_RN6, /* {u16 index, value}: 8 / 20 B; absent from files written before they existed */
-       MIR_LAST = MIR_RN6 };
+       /* {endpoint key, endpoint_info}: 68 B, the endpoints of MIR_EP whose value is
+	* not all-zero; {tunnel key, value}: 40 B.  Each written only when it has a
+	* record, so a mirror that never used them saves the file it always did */
+       MIR_EPI, MIR_TUN,
+       MIR_LAST = MIR_TUN };
 
 struct MirOut {
 	std::vector<uint8_t> buf;
@@ -6983,6 +7323,26 @@ CGPU_EXPORT int cgpu_mirror_save(cgpu_ctx *c, const char *path)
 			o.put(kv.second);
 		}
 		o.count(at, c->rn6.size());
+		uint32_t nsec = 12;
+		if (!c->lxc_info.empty()) {
+			at = o.section(MIR_EPI, 68);
+			for (auto &kv : c->lxc_info) {
+				o.put(kv.first.data(), 20);
+				o.put(kv.second);
+			}
+			o.count(at, c->lxc_info.size());
+			nsec++;
+		}
+		if (!c->tun.empty()) {
+			at = o.section(MIR_TUN, 40);
+			for (auto &kv : c->tun) {
+				o.put(kv.first.data(), 20);
+				o.put(kv.second.data(), 20);
+			}
+			o.count(at, c->tun.size());
+			nsec++;
+		}
+		memcpy(&o.buf[12], &nsec, 4);
 	}
 	o.put(fnv(1469598103934665603ull, o.buf.data(), o.buf.size()));
 	const std::string tmp = std::string(path) + ".tmp";
@@ -7098,6 +7458,14 @@ static void mirror_rollback(cgpu_ctx *c, const std::vector<uint8_t> &buf, const 
 					cgpu_revnat6_delete(c, index);
 				break;
 			}
+			case MIR_EPI: /* its key is a MIR_EP record: deleted there, value and all */
+				break;
+			case MIR_TUN: {
+				cgpu_endpoint_key key;
+				memcpy(&key, r, 20);
+				cgpu_tunnel_delete(c, &key);
+				break;
+			}
 			}
 		}
 	}
@@ -7133,7 +7501,7 @@ CGPU_EXPORT int cgpu_mirror_restore(cgpu_ctx *c, const char *path)
 		std::lock_guard<std::mutex> g(c->mu);
 		bool empty = c->ipc.empty() && !c->pol_total && c->dyn4.empty() && c->dyn6.empty() &&
 			     c->fix4.empty() && c->fix6.empty() && c->lxc.empty() && c->lb.empty() &&
-			     c->lb6.empty() && c->lxcinfo.empty() && c->rn4.empty() && c->rn6.empty();
+			     c->lb6.empty() && c->lxcinfo.empty() && c->rn4.empty() && c->rn6.empty() && c->tun.empty();
 		for (CtMap *m : {&c->ct4, &c->ct6}) {
 			if (int r = ct_pull(c, *m))
 				return r;
@@ -7147,7 +7515,7 @@ CGPU_EXPORT int cgpu_mirror_restore(cgpu_ctx *c, const char *path)
 	std::vector<Sec> secs;
 	size_t off = 16;
 	const size_t end = buf.size() - 8;
-	static const uint32_t recsz[] = {0, 32, 36, 24, 20, 20, 44, 36, 8, 70, 94, 8, 20};
+	static const uint32_t recsz[] = {0, 32, 36, 24, 20, 20, 44, 36, 8, 70, 94, 8, 20, 68, 40};
 	for (uint32_t i = 0; i < nsec; i++) {
 		Sec s_;
 		if (off + 16 > end)
@@ -7188,7 +7556,8 @@ CGPU_EXPORT int cgpu_mirror_restore(cgpu_ctx *c, const char *path)
 			   {MIR_LB4, cap.lb, "lb_max_entries (lb4)"}, {MIR_LB6, cap.lb, "lb_max_entries (lb6)"},
 			   {MIR_CT4, cap.ct4, "ct_max"},              {MIR_CT6, cap.ct6, "ct6_max"},
 			   {MIR_RN4, cap.lb, "lb_max_entries (reverse NAT 4)"},
-			   {MIR_RN6, cap.lb, "lb_max_entries (reverse NAT 6)"}};
+			   {MIR_RN6, cap.lb, "lb_max_entries (reverse NAT 6)"},
+			   {MIR_TUN, CGPU_TUNNEL_MAP_SIZE, "the tunnel map's size"}};
 		for (const auto &l : lim)
 			if (cnt[l.tag] > l.max)
 				return fail(-E2BIG, "%s: %llu records exceed this context's %s (%llu)", path,
@@ -7304,6 +7673,21 @@ CGPU_EXPORT int cgpu_mirror_restore(cgpu_ctx *c, const char *path)
 				memcpy(&index, r, 2);
 				memcpy(&v, r + 2, 18);
 				rc = cgpu_revnat6_update(c, index, &v, CGPU_NOEXIST);
+				break;
+			}
+			case MIR_EPI: {
+				cgpu_endpoint_key k;
+				cgpu_endpoint_info v;
+				memcpy(&k, r, 20);
+				memcpy(&v, r + 20, 48);
+				rc = cgpu_endpoint_update_info(c, &k, &v, CGPU_EXIST);
+				break;
+			}
+			case MIR_TUN: {
+				cgpu_endpoint_key k, v;
+				memcpy(&k, r, 20);
+				memcpy(&v, r + 20, 20);
+				rc = cgpu_tunnel_update(c, &k, &v, CGPU_NOEXIST);
 				break;
 			}
 			}

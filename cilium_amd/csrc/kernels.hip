@@ -3794,6 +3794,178 @@ __global__ __launch_bounds__(BLOCK) void k_ipcache_lookup(lpm16c id4, v6_lpm id6
 	}
 }
 
+/* ---- forwarding tables (tables.h fwd_tables) ---- */
+
+/* the 16-B slot holding `key` (word x), given its home slot q: usually q
+ * itself; only other set hop bits cost further loads */
+__device__ __forceinline__ bool fwd_find4(const uint4 *t, uint32_t mask, uint32_t home, uint32_t key, uint4 q,
+					  uint4 &hit)
+{
+	uint32_t hop = q.w >> POL_HOP_SHIFT;
+	while (hop) {
+		const uint32_t j = (uint32_t)__ffs((int)hop) - 1u;
+		hop &= hop - 1u;
+		if (j)
+			q = t[(home + j) & mask];
+		if (q.x == key) {
+			hit = q;
+			return true;
+		}
+	}
+	return false;
+}
+
+/* the 32-B row whose first NK words are `key`, given its home row (q0, q1) */
+template <int NK>
+__device__ __forceinline__ bool fwd_find6(const uint4 *t, uint32_t mask, uint32_t home, uint4 key, uint4 q0,
+					  uint4 q1, uint4 &h0, uint4 &h1)
+{
+	uint32_t hop = q1.z >> POL_HOP_SHIFT;
+	while (hop) {
+		const uint32_t j = (uint32_t)__ffs((int)hop) - 1u;
+		hop &= hop - 1u;
+		if (j) {
+			const uint4 *r = t + 2u * (size_t)((home + j) & mask);
+			q0 = r[0];
+			q1 = r[1];
+		}
+		if (q0.x == key.x && q0.y == key.y && q0.z == key.z && (NK == 3 || q0.w == key.w)) {
+			h0 = q0;
+			h1 = q1;
+			return true;
+		}
+	}
+	return false;
+}
+
+/* Forwarding decision of allowed packets (cgpu_forward_v4 / _v6; the decision
+ * lists are in include/cgpu.h): the rest of handle_ipv4_from_lxc /
+ * ipv6_l3_from_lxc (bpf_lxc.c:547-657, :242-354; MODE CGPU_FWD_LXC) and of the
+ * netdev's handle_ipv4 / handle_ipv6 (bpf_netdev.c:422-452, :240-274).  One
+ * packet per lane in batch order, grid-stride; the columns stream past the
+ * tables (nontemporal).  The endpoint's home slot and, in the ENCAP build,
+ * the tunnel map's are gathered together by every lane, before anything is
+ * decided: a lane that turns out not to need one drops it (a per-lane branch
+ * around a load would serialise the two round trips).  Without
+ * forwarding tables (F.e4 == NULL) the snapshot's endpoint sets answer with
+ * all-zero values and the tunnel map is empty. */
+template <bool V6, int MODE>
+__global__ __launch_bounds__(BLOCK) void k_forward(fwd_tables F, fwd_args a)
+{
+	const uint64_t stride = (uint64_t)gridDim.x * BLOCK;
+	const uint32_t al = ((uintptr_t)a.daddr & 15u) == 0 ? 0u : (((uintptr_t)a.daddr & 3u) == 0 ? 1u : 2u);
+	const bool built = F.e4 != nullptr;
+	const bool encap = a.encap != 0u;
+	for (uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i < a.n; i += stride) {
+		uint4 da = make_uint4(0, 0, 0, 0);
+		if (V6) {
+			const uint8_t *p = static_cast<const uint8_t *>(a.daddr) + 16u * i;
+			da = al == 0 ? ld_x4<true>(p) : ld_addr16(p, al);
+		} else {
+			da.x = ntl(static_cast<const uint32_t *>(a.daddr) + i);
+		}
+		const int32_t verdict = MODE == CGPU_FWD_LXC ? (int32_t)ntl(a.verdict + i) : 0;
+		const bool egress = MODE == CGPU_FWD_LXC ? (ntl(a.flags + i) & CGPU_F_EGRESS) != 0u : true;
+		const uint32_t tun = a.tunnel ? ntl(a.tunnel + i) : 0u;
+		const bool expired = a.ttl ? ntl(a.ttl + i) <= 1u : false;
+
+		bool ep_hit = false, tm_hit = false;
+		uint32_t ep_if = 0, ep_w = 0, tm_ip = 0;
+		if (built) {
+			if (V6) {
+				const uint32_t he = fold6(da.x, da.y, da.z, da.w) & F.e6_mask;
+				const uint32_t ht = fold6(da.x, da.y, da.z, 0u) & F.t6_mask;
+				const uint4 *re = F.e6 + 2u * (size_t)he, *rt = F.t6 + 2u * (size_t)ht;
+				const uint4 e0 = re[0], e1 = re[1];
+				uint4 t0 = make_uint4(0, 0, 0, 0), t1 = t0, h0, h1;
+				if (encap) {
+					t0 = rt[0];
+					t1 = rt[1];
+				}
+				if (fwd_find6<4>(F.e6, F.e6_mask, he, da, e0, e1, h0, h1)) {
+					ep_hit = true;
+					ep_if = h1.x;
+					ep_w = h1.y;
+				}
+				if (encap && fwd_find6<3>(F.t6, F.t6_mask, ht, da, t0, t1, h0, h1)) {
+					tm_hit = true;
+					tm_ip = h0.w;
+				}
+			} else {
+				const uint32_t tk = da.x & a.ipv4_mask;
+				const uint32_t he = fwd_hash4(da.x) & F.e4_mask, ht = fwd_hash4(tk) & F.t4_mask;
+				const uint4 e = F.e4[he];
+				uint4 t = make_uint4(0, 0, 0, 0), h;
+				if (encap)
+					t = F.t4[ht];
+				if (fwd_find4(F.e4, F.e4_mask, he, da.x, e, h)) {
+					ep_hit = true;
+					ep_if = h.y;
+					ep_w = h.z;
+				}
+				if (encap && fwd_find4(F.t4, F.t4_mask, ht, tk, t, h)) {
+					tm_hit = true;
+					tm_ip = h.y;
+				}
+			}
+		} else if (V6) {
+			const uint32_t b = pfx6_hash(da.x, da.y, da.z, da.w, 0u) & a.ep6.bucket_mask;
+			const uint4 *p = reinterpret_cast<const uint4 *>(a.ep6.slots) + (size_t)b * 4u;
+			ep_hit = set16_has_first(a.ep6, p[0], p[1].x, p[2], p[3].x, b, da);
+		} else {
+			ep_hit = set4_has(a.ep4, da.x);
+		}
+
+		const bool gate = MODE == CGPU_FWD_LXC
+					  ? true
+					  : (V6 ? da.x == a.router[0] && da.y == a.router[1] && da.z == a.router[2]
+						: (da.x & a.cluster_mask) == a.cluster_range);
+		const bool host = (ep_w & FWD_HOST_BIT) != 0u;
+		uint32_t act, ifx = 0, arg = 0;
+		int32_t ret = 0;
+		bool l3 = false; /* the branch runs ipv4_l3 / ipv6_l3: ttl / hop limit */
+		if (MODE == CGPU_FWD_LXC && !egress) {
+			act = CGPU_FWD_NONE;
+		} else if (MODE == CGPU_FWD_LXC && verdict < 0) {
+			act = CGPU_FWD_DROP;
+			ret = verdict;
+		} else if (MODE == CGPU_FWD_LXC && verdict > 0) {
+			act = CGPU_FWD_PROXY;
+			arg = (uint32_t)verdict;
+			ifx = a.host_ifindex;
+			l3 = true;
+		} else if (ep_hit && host) {
+			act = MODE == CGPU_FWD_LXC ? CGPU_FWD_HOST : CGPU_FWD_STACK;
+			ifx = MODE == CGPU_FWD_LXC ? a.host_ifindex : 0u;
+			l3 = MODE == CGPU_FWD_LXC;
+		} else if (ep_hit) {
+			act = CGPU_FWD_LOCAL;
+			ifx = ep_if;
+			arg = ep_w & 0xFFFFu;
+			l3 = true;
+		} else if (encap && (tun != 0u || (gate && tm_hit))) {
+			act = CGPU_FWD_OVERLAY;
+			arg = tun != 0u ? tun : tm_ip;
+			ifx = a.encap_ifindex;
+		} else {
+			act = CGPU_FWD_STACK;
+			l3 = MODE == CGPU_FWD_LXC;
+		}
+		if (l3 && expired) {
+			act = V6 ? CGPU_FWD_TIME_EXCEEDED : CGPU_FWD_DROP;
+			ret = V6 ? 0 : CGPU_DROP_INVALID;
+			ifx = arg = 0u;
+		}
+		__builtin_nontemporal_store((uint8_t)act, a.action + i);
+		if (a.ret)
+			__builtin_nontemporal_store(ret, a.ret + i);
+		if (a.ifindex)
+			__builtin_nontemporal_store(ifx, a.ifindex + i);
+		if (a.arg)
+			__builtin_nontemporal_store(arg, a.arg + i);
+	}
+}
+
 unsigned grid_for(uint64_t n)
 {
 	uint64_t blocks = (n + BLOCK - 1) / BLOCK;
@@ -4225,6 +4397,33 @@ hipError_t launch_ipcache_lookup(const cgpu_snapshot &s, const ipc_tun &t, const
 			hipLaunchKernelGGL((k_ipcache_lookup<false, true>), g, b, 0, st, s.ipc4c, s.ipc6, t, a);
 		else
 			hipLaunchKernelGGL((k_ipcache_lookup<false, false>), g, b, 0, st, s.ipc4c, s.ipc6, t, a);
+	}
+	return hipGetLastError();
+}
+
+hipError_t launch_forward(const cgpu_snapshot &s, const fwd_tables &f, const fwd_args &x, hipStream_t st)
+{
+	if (!x.n)
+		return hipSuccess;
+	fwd_args a = x;
+	a.ep4 = s.ep4;
+	a.ep6 = s.ep6;
+	a.cluster_mask = s.ipv4_cluster_mask;
+	a.cluster_range = s.ipv4_cluster_range;
+	a.router[0] = s.router_ip[0];
+	a.router[1] = s.router_ip[1];
+	a.router[2] = s.router_ip[2];
+	const dim3 g(grid_for(a.n)), b(BLOCK);
+	if (a.v6) {
+		if (a.mode == CGPU_FWD_NETDEV)
+			hipLaunchKernelGGL((k_forward<true, CGPU_FWD_NETDEV>), g, b, 0, st, f, a);
+		else
+			hipLaunchKernelGGL((k_forward<true, CGPU_FWD_LXC>), g, b, 0, st, f, a);
+	} else {
+		if (a.mode == CGPU_FWD_NETDEV)
+			hipLaunchKernelGGL((k_forward<false, CGPU_FWD_NETDEV>), g, b, 0, st, f, a);
+		else
+			hipLaunchKernelGGL((k_forward<false, CGPU_FWD_LXC>), g, b, 0, st, f, a);
 	}
 	return hipGetLastError();
 }

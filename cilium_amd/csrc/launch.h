@@ -75,6 +75,28 @@ struct ipc_lookup_args {
 hipError_t launch_ipcache_lookup(const cgpu_snapshot &s, const ipc_tun &t, const ipc_lookup_args &a,
 				 hipStream_t st);
 
+/* forwarding decision (cgpu_forward_v4 / _v6): the columns of cgpu_fwd_in /
+ * cgpu_fwd_out and the words of cgpu_fwd_params; the snapshot's parts the
+ * kernel reads (endpoint sets for a context without forwarding tables, the
+ * netdev gate's config words) are filled in by launch_forward */
+struct fwd_args {
+	const void *daddr;
+	const int32_t *verdict;
+	const uint32_t *tunnel;
+	const uint8_t *flags, *ttl;
+	uint8_t *action;
+	int32_t *ret;
+	uint32_t *ifindex, *arg;
+	uint64_t n;
+	uint32_t mode, encap, ipv4_mask, host_ifindex, encap_ifindex;
+	int v6;
+	addr_set4 ep4;
+	addr_set16 ep6;
+	uint32_t cluster_mask, cluster_range, router[3];
+};
+
+hipError_t launch_forward(const cgpu_snapshot &s, const fwd_tables &f, const fwd_args &a, hipStream_t st);
+
 struct prefilter_args {
 	const uint32_t *saddr4, *daddr4;
 	const uint8_t *saddr16, *daddr16;

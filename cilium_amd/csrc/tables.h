@@ -506,6 +506,42 @@ typedef struct ipc_tun {
 	v6_lpm t6;
 } ipc_tun;
 
+/* ---- forwarding tables (cgpu_forward_v4 / _v6) ----
+ * cilium_lxc WITH its values and cilium_tunnel_map, as four single-slot
+ * neighbourhood hashes (POL_HOP scheme: hop bits 24..31 of the slot's tag
+ * word, bit j of home slot h = "slot h + j holds a key whose home is h"), so
+ * that a lookup is one gather of a line that already carries the value:
+ *   e4: 16-B slots {addr, ifindex, lxc_id | host << 16, FWD_USED | hop << 24},
+ *       home = fwd_hash4(addr); host = endpoint_info.flags & ENDPOINT_F_HOST,
+ *       the only flag the programs read;
+ *   e6: 32-B rows {addr raw words}, {ifindex, lxc_id | host << 16,
+ *       FWD_USED | hop << 24, 0}, home = fold6(addr);
+ *   t4: 16-B slots {key.ip4, value.ip4, 0, FWD_USED | hop << 24}, home =
+ *       fwd_hash4(key.ip4);
+ *   t6: 32-B rows {p1, p2, p3, value.ip4}, {0, 0, FWD_USED | hop << 24, 0},
+ *       home = fold6(p1, p2, p3, 0).
+ * Only keys the programs can build are stored (zero pad bytes, the family's
+ * tag, IPv4: zero pad words, IPv6 tunnel: p4 == 0); any other map key never
+ * matches.  Kept beside the snapshot, not in it, and built only when some
+ * endpoint has a non-zero value or the tunnel map holds a key; e4 == NULL:
+ * not built (the endpoint sets of the snapshot answer, every value 0, and
+ * the tunnel map is empty).  Built, all four tables exist. */
+#define FWD_USED 1u
+#define FWD_HOST_BIT (1u << 16)
+
+typedef struct fwd_tables {
+	const uint4 *e4; /* e4_mask + 1 slots; NULL = not built */
+	const uint4 *e6; /* (e6_mask + 1) x 2 */
+	const uint4 *t4; /* t4_mask + 1 slots */
+	const uint4 *t6; /* (t6_mask + 1) x 2 */
+	uint32_t e4_mask, e6_mask, t4_mask, t6_mask;
+} fwd_tables;
+
+static inline __host__ __device__ uint32_t fwd_hash4(uint32_t a)
+{
+	return mix32(a, 0x46574434u);
+}
+
 /* ---- conntrack map cilium_ct4_global ----
  * Open addressing with linear probing over nslots = 2^k >= 2 * max slots.
  * keys[slot] (16 B, one gather per probe) = the 14-byte struct ipv4_ct_tuple

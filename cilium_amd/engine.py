@@ -25,8 +25,8 @@ import ipaddress
 import numpy as np
 
 from . import layouts as L
-from ._abi import (CgpuConfig, CgpuError, CtlbOut, FrameTuples, Frames, Lb4Out, Lb4Tuples, Rnat4Out,
-                   Rnat6Out, TuplesV4, TuplesV4Ct, TuplesV6Ct, TuplesV6, check, lib)
+from ._abi import (CgpuConfig, CgpuError, CtlbOut, FrameTuples, Frames, FwdIn, FwdOut, FwdParams, Lb4Out,
+                   Lb4Tuples, Rnat4Out, Rnat6Out, TuplesV4, TuplesV4Ct, TuplesV6Ct, TuplesV6, check, lib)
 
 CIDR_V4_DYN, CIDR_V4_FIX, CIDR_V6_DYN, CIDR_V6_FIX = 0, 1, 2, 3
 BPF_ANY, BPF_NOEXIST, BPF_EXIST = 0, 1, 2
@@ -194,8 +194,41 @@ class Engine:
             keys.append(np.frombuffer(prev[:dt.itemsize], dt)[0])
         return keys
 
-    def endpoint_update(self, key, flags=BPF_ANY) -> int:
+    def endpoint_update(self, key, flags=BPF_ANY, info=None) -> int:
+        """info: an L.ENDPOINT_INFO value (cgpu_endpoint_update_info); None
+        writes the all-zero value."""
+        if info is not None:
+            return self.L.cgpu_endpoint_update_info(self.h, _buf(key), _buf(np.asarray(info, L.ENDPOINT_INFO)),
+                                                    flags)
         return self.L.cgpu_endpoint_update(self.h, _buf(key), flags)
+
+    def endpoint_lookup_info(self, key):
+        out = C.create_string_buffer(48)
+        rc = self.L.cgpu_endpoint_lookup_info(self.h, _buf(key), out)
+        return rc, (np.frombuffer(out.raw, L.ENDPOINT_INFO)[0] if rc == 0 else None)
+
+    # --- cilium_tunnel_map (key and value: raw 20-byte endpoint keys) ---
+    def tunnel_update(self, key, val, flags=BPF_ANY) -> int:
+        return self.L.cgpu_tunnel_update(self.h, _buf(key), _buf(val), flags)
+
+    def tunnel_delete(self, key) -> int:
+        return self.L.cgpu_tunnel_delete(self.h, _buf(key))
+
+    def tunnel_lookup(self, key):
+        out = C.create_string_buffer(20)
+        rc = self.L.cgpu_tunnel_lookup(self.h, _buf(key), out)
+        return rc, (np.frombuffer(out.raw, L.ENDPOINT_KEY)[0] if rc == 0 else None)
+
+    def tunnel_keys(self):
+        keys, prev = [], None
+        out = C.create_string_buffer(20)
+        while self.L.cgpu_tunnel_get_next_key(self.h, prev, out) == 0:
+            prev = out.raw
+            keys.append(np.frombuffer(prev, L.ENDPOINT_KEY)[0])
+        return keys
+
+    def tunnel_count(self) -> int:
+        return self.L.cgpu_tunnel_count(self.h)
 
     def endpoint_delete(self, key) -> int:
         return self.L.cgpu_endpoint_delete(self.h, _buf(key))
@@ -510,10 +543,17 @@ class Engine:
         return out
 
     def classify_v4(self, t: dict, out: dict | None = None, stage: bool = True, stream=None,
-                    tunnel: bool = False):
+                    tunnel: bool = False, forward: dict | None = None):
         """t: dict of CUDA tensors saddr/daddr (int32 view of network-order
         u32), dport (int16), proto/flags (uint8), len (int32), ep (int16).
-        tunnel=True: out["tunnel"] too (_classify_tun)."""
+        tunnel=True: out["tunnel"] too (_classify_tun).  forward=<dict of
+        forward_v4's mode / encap / ipv4_mask / host_ifindex / encap_ifindex>:
+        the tunnel form, then the forwarding step on its outputs into
+        out["fwd_action"], ["fwd_ret"], ["fwd_ifindex"], ["fwd_arg"]
+        (_forward_into; t may hold "ttl")."""
+        if forward is not None:
+            out = self._classify_tun(False, self.PATH_PLAIN, t, out, stage, stream)
+            return self._forward_into(False, t, out, forward, stream)
         if tunnel:
             return self._classify_tun(False, self.PATH_PLAIN, t, out, stage, stream)
         import torch
@@ -613,7 +653,8 @@ class Engine:
         return out
 
     def classify_v4_ct(self, t: dict, now: int, out: dict | None = None, stage: bool = True,
-                       stream=None, tunnel: bool = False, rev_nat: bool = False):
+                       stream=None, tunnel: bool = False, rev_nat: bool = False,
+                       forward: dict | None = None):
         """Stateful classification (cgpu_classify_v4_ct): t holds CUDA tensors
         saddr/daddr (int32), sport/dport (int16, network order), proto/flags
         (uint8), l4b (int16: TCP header bytes 12-13 / ICMP type), len (int32),
@@ -621,9 +662,12 @@ class Engine:
         tunnel=True: out["tunnel"] too (_ct_tun).  rev_nat=True
         (cgpu_classify_v4_ct_rnat): out["rn_saddr"], ["rn_daddr"] (int32),
         ["rn_sport"] (int16), ["rn_applied"] (uint8), the frame after the
-        replies' reverse NAT."""
-        if tunnel and rev_nat:
-            raise ValueError("tunnel and rev_nat cannot be combined")
+        replies' reverse NAT.  forward=: as classify_v4, on the tunnel form."""
+        if (tunnel or forward is not None) and rev_nat:
+            raise ValueError("tunnel / forward and rev_nat cannot be combined")
+        if forward is not None:
+            out = self._ct_tun(False, t, now, out, stage, stream)
+            return self._forward_into(False, t, out, forward, stream)
         if tunnel:
             return self._ct_tun(False, t, now, out, stage, stream)
         import torch
@@ -668,11 +712,12 @@ class Engine:
         return Rnat4Out(*[out[k].data_ptr() for k in ("rn_saddr", "rn_daddr", "rn_sport", "rn_applied")])
 
     def classify_v4_ctlb(self, t: dict, now: int, out: dict | None = None, stage: bool = True,
-                         xlate: bool = True, stream=None, rev_nat: bool = False):
+                         xlate: bool = True, stream=None, rev_nat: bool = False, forward=None):
         """cgpu_classify_v4_ctlb: classify_v4_ct with the stateful service
         step (lb4_local with CONNTRACK) in front; t may carry a "hash" column
         (skb->hash, int32).  out adds "daddr" / "dport": the frame after the
         service step (xlate=False: not written)."""
+        self._no_forward(forward, "classify_v4_ctlb")
         import torch
         n = t["saddr"].numel()
         dev = t["saddr"].device
@@ -698,12 +743,16 @@ class Engine:
         return out
 
     def classify_v6_ct(self, t: dict, now: int, out: dict | None = None, stage: bool = True,
-                       stream=None, tunnel: bool = False, rev_nat: bool = False):
+                       stream=None, tunnel: bool = False, rev_nat: bool = False,
+                       forward: dict | None = None):
         """cgpu_classify_v6_ct: as classify_v4_ct with saddr / daddr (n, 16)
         uint8 tensors (16-byte aligned rows).  rev_nat=True: out["rn_saddr"]
         (n, 16) uint8, ["rn_sport"], ["rn_applied"] (IPv6 has no rn_daddr)."""
-        if tunnel and rev_nat:
-            raise ValueError("tunnel and rev_nat cannot be combined")
+        if (tunnel or forward is not None) and rev_nat:
+            raise ValueError("tunnel / forward and rev_nat cannot be combined")
+        if forward is not None:
+            out = self._ct_tun(True, t, now, out, stage, stream)
+            return self._forward_into(True, t, out, forward, stream)
         if tunnel:
             return self._ct_tun(True, t, now, out, stage, stream)
         import torch
@@ -730,10 +779,11 @@ class Engine:
         return out
 
     def classify_v6_ctlb(self, t: dict, now: int, out: dict | None = None, stage: bool = True,
-                         xlate: bool = True, stream=None, rev_nat: bool = False):
+                         xlate: bool = True, stream=None, rev_nat: bool = False, forward=None):
         """cgpu_classify_v6_ctlb: classify_v6_ct with the stateful service
         step (lb6_local with CONNTRACK) in front; out "daddr" is (n, 16)
         uint8."""
+        self._no_forward(forward, "classify_v6_ctlb")
         import torch
         n = t["saddr"].shape[0]
         dev = t["saddr"].device
@@ -759,12 +809,13 @@ class Engine:
         return out
 
     def classify_v4_lb(self, t: dict, out: dict | None = None, stage: bool = True, stream=None,
-                       xdp: bool = False, tunnel: bool = False):
+                       xdp: bool = False, tunnel: bool = False, forward=None):
         """classify_v4 with the egress service step first (BASELINE config 5).
         t additionally holds "hash" (int32 view of skb->hash) or "sport".
         xdp=True: cgpu_classify_v4_cascade, the netdev's XDP prefilter before
         every ingress tuple too (the full config-5 cascade).
         tunnel=True: out["tunnel"] too (_classify_tun)."""
+        self._no_forward(forward, "classify_v4_cascade" if xdp else "classify_v4_lb")
         if tunnel:
             return self._classify_tun(False, self.PATH_CASCADE if xdp else self.PATH_LB, t, out, stage,
                                       stream)
@@ -784,11 +835,12 @@ class Engine:
         return out
 
     def classify_v4_cascade(self, t: dict, out: dict | None = None, stage: bool = True, stream=None,
-                            tunnel: bool = False):
+                            tunnel: bool = False, forward=None):
         """BASELINE config 5 whole (cgpu_classify_v4_cascade): XDP prefilter
         -> ipcache -> policy for ingress tuples, service step -> ipcache ->
         policy for egress ones."""
-        return self.classify_v4_lb(t, out=out, stage=stage, stream=stream, xdp=True, tunnel=tunnel)
+        return self.classify_v4_lb(t, out=out, stage=stage, stream=stream, xdp=True, tunnel=tunnel,
+                                   forward=forward)
 
     def lb4_select(self, t: dict, mode: int, out: dict | None = None, stream=None):
         """Service translation alone: t holds saddr/daddr (int32 views),
@@ -812,9 +864,12 @@ class Engine:
         return out
 
     def classify_v6(self, t: dict, out: dict | None = None, stage: bool = True, stream=None,
-                    tunnel: bool = False):
+                    tunnel: bool = False, forward: dict | None = None):
         """t: saddr/daddr uint8 CUDA tensors of shape (n, 16) (16-byte
-        aligned), the other columns as classify_v4."""
+        aligned), the other columns as classify_v4 (forward= too)."""
+        if forward is not None:
+            out = self._classify_tun(True, self.PATH_PLAIN, t, out, stage, stream)
+            return self._forward_into(True, t, out, forward, stream)
         if tunnel:
             return self._classify_tun(True, self.PATH_PLAIN, t, out, stage, stream)
         import torch
@@ -832,9 +887,10 @@ class Engine:
         return out
 
     def classify_v6_lb(self, t: dict, out: dict | None = None, stage: bool = True, stream=None,
-                       tunnel: bool = False):
+                       tunnel: bool = False, forward=None):
         """classify_v6 with the egress service step of ipv6_l3_from_lxc first;
         t additionally holds "hash" (int32 view of skb->hash) or "sport"."""
+        self._no_forward(forward, "classify_v6_lb")
         if tunnel:
             return self._classify_tun(True, self.PATH_LB, t, out, stage, stream)
         import torch
@@ -878,6 +934,75 @@ class Engine:
         check(getattr(self.L, fn)(self.h, _ptr(addr), n, _ptr(out["found"]), _ptr(out["sec_label"]),
                                   _ptr(out["tunnel"]), _stream(stream)), fn)
         return out
+
+    FWD_LXC, FWD_NETDEV = L.FWD_LXC, L.FWD_NETDEV
+    _FWD_KEYS = ("mode", "encap", "ipv4_mask", "host_ifindex", "encap_ifindex")
+
+    def _forward(self, v6: bool, daddr, verdict, tunnel, flags, ttl, mode, encap, ipv4_mask, host_ifindex,
+                 encap_ifindex, out, stream):
+        import torch
+        n = daddr.shape[0]
+        dev = daddr.device
+        if out is None:
+            out = {"action": torch.empty(n, dtype=torch.uint8, device=dev),
+                   "ret": torch.empty(n, dtype=torch.int32, device=dev),
+                   "ifindex": torch.empty(n, dtype=torch.int32, device=dev),
+                   "arg": torch.empty(n, dtype=torch.int32, device=dev)}
+        p = FwdParams(mode, L.FWD_ENCAP if encap else 0, ipv4_mask, host_ifindex, encap_ifindex)
+        iv = FwdIn(*[x.data_ptr() if x is not None else None for x in (daddr, verdict, tunnel, flags, ttl)])
+        ov = FwdOut(*[out[k].data_ptr() if out.get(k) is not None else None
+                      for k in ("action", "ret", "ifindex", "arg")])
+        fn = "cgpu_forward_v6" if v6 else "cgpu_forward_v4"
+        check(getattr(self.L, fn)(self.h, C.byref(p), C.byref(iv), n, C.byref(ov), _stream(stream)), fn)
+        return out
+
+    def forward_v4(self, daddr, verdict=None, tunnel=None, flags=None, ttl=None, mode=L.FWD_LXC,
+                   encap=True, ipv4_mask=0xffff, host_ifindex=1, encap_ifindex=1, out=None, stream=None):
+        """cgpu_forward_v4: where each packet of an allowed batch goes
+        (include/cgpu.h has the decision lists).  daddr: int32 / uint32 CUDA
+        tensor as it leaves the classify step; verdict (int32) and flags
+        (uint8) of that step (FWD_NETDEV reads neither); tunnel: the raw
+        tunnel_endpoint words (int32 / uint32; None = all 0); ttl (uint8; None
+        = never expired).  Returns {"action" (uint8, L.FWD_*), "ret",
+        "ifindex", "arg"} (int32 tensors holding the raw words); a given `out`
+        may leave any of the last three None."""
+        return self._forward(False, daddr, verdict, tunnel, flags, ttl, mode, encap, ipv4_mask,
+                             host_ifindex, encap_ifindex, out, stream)
+
+    def forward_v6(self, daddr, verdict=None, tunnel=None, flags=None, ttl=None, mode=L.FWD_LXC,
+                   encap=True, ipv4_mask=0xffff, host_ifindex=1, encap_ifindex=1, out=None, stream=None):
+        """cgpu_forward_v6: forward_v4 with daddr an (n, 16) uint8 tensor at
+        any alignment and ttl the hop limit."""
+        return self._forward(True, daddr, verdict, tunnel, flags, ttl, mode, encap, ipv4_mask,
+                             host_ifindex, encap_ifindex, out, stream)
+
+    def forward_table_bytes(self) -> dict:
+        """cgpu_forward_table_bytes: device bytes of the forwarding tables (all
+        0 while they are not built)."""
+        b = (C.c_uint64 * 4)()
+        check(self.L.cgpu_forward_table_bytes(self.h, b), "cgpu_forward_table_bytes")
+        return dict(zip(("endpoints4", "endpoints6", "tunnel4", "tunnel6"), (int(x) for x in b)))
+
+    def _forward_into(self, v6: bool, t: dict, out: dict, forward: dict, stream):
+        """forward=<forward_v4's keyword parameters> of a classify call: the
+        forwarding step on the call's own daddr, verdict, tunnel and flags
+        (and t["ttl"] when present), into out["fwd_*"]."""
+        bad = set(forward) - set(self._FWD_KEYS)
+        if bad:
+            raise TypeError(f"unknown forward parameter(s) {sorted(bad)}")
+        given = {k: out.get("fwd_" + k) for k in ("action", "ret", "ifindex", "arg")}
+        f = (self.forward_v6 if v6 else self.forward_v4)(
+            t["daddr"], verdict=out["verdict"], tunnel=out["tunnel"], flags=t["flags"], ttl=t.get("ttl"),
+            out=given if given["action"] is not None else None, stream=stream, **forward)
+        for k, v in f.items():
+            out["fwd_" + k] = v
+        return out
+
+    @staticmethod
+    def _no_forward(forward, what: str):
+        if forward is not None:
+            raise ValueError(f"{what} has no forward= form: the translated daddr and the tunnel endpoint "
+                             "are not outputs of the service paths")
 
     def prefilter_v4(self, saddr, daddr, flags, out=None, stream=None):
         import torch
@@ -1248,3 +1373,39 @@ class LBMap:
 
     def DumpServiceMapsToUserspace(self):  # noqa: N802
         return [(k, self.e.lb4_lookup(k)[1]) for k in self.e.lb4_keys()]
+
+
+class LXCMap:
+    """pkg/maps/lxcmap/lxcmap.go:154-198 over cilium_lxc with its values."""
+
+    def __init__(self, engine: Engine):
+        self.e = engine
+
+    def WriteEndpoint(self, ips, ifindex: int, lxc_id: int, mac=0, node_mac=0):  # noqa: N802
+        """One endpoint_info under every key of the endpoint (GetBPFKeys:
+        its IPv4 and IPv6 address)."""
+        info = L.endpoint_info(ifindex, lxc_id, 0, mac, node_mac)
+        for ip in ([ips] if isinstance(ips, str) else ips):
+            check(self.e.endpoint_update(L.endpoint_key(ip), BPF_ANY, info), "WriteEndpoint")
+
+    def AddHostEntry(self, ip: str):  # noqa: N802
+        check(self.e.endpoint_update(L.endpoint_key(ip), BPF_ANY, L.endpoint_info(flags=L.ENDPOINT_F_HOST)),
+              "AddHostEntry")
+
+    def DeleteEntry(self, ip: str):  # noqa: N802
+        if self.e.endpoint_delete(L.endpoint_key(ip)) != 0:
+            raise CgpuError(errno.ENOENT, f"endpoint {ip} not found")
+
+
+class TunnelMap:
+    """pkg/maps/tunnel/tunnel.go:83-99 over cilium_tunnel_map."""
+
+    def __init__(self, engine: Engine):
+        self.e = engine
+
+    def SetTunnelEndpoint(self, prefix: str, endpoint: str):  # noqa: N802
+        check(self.e.tunnel_update(L.endpoint_key(prefix), L.endpoint_key(endpoint)), "SetTunnelEndpoint")
+
+    def DeleteTunnelEndpoint(self, prefix: str):  # noqa: N802
+        if self.e.tunnel_delete(L.endpoint_key(prefix)) != 0:
+            raise CgpuError(errno.ENOENT, f"tunnel prefix {prefix} not found")

@@ -241,6 +241,35 @@ def endpoint_key(ip: str) -> np.ndarray:
     return k
 
 
+# struct endpoint_info, bpf/lib/common.h:165-173 (48 B; mac_t is __u64, so the
+# C layout has a 4-byte hole before `mac`): the value of cilium_lxc
+ENDPOINT_INFO = np.dtype([("ifindex", "<u4"), ("unused", "<u2"), ("lxc_id", "<u2"), ("flags", "<u4"),
+                          ("pad0", "<u4"), ("mac", "<u8"), ("node_mac", "<u8"), ("pad", "<u4", (4,))])
+assert ENDPOINT_INFO.itemsize == 48
+ENDPOINT_F_HOST = 1
+
+# the forwarding step (include/cgpu.h cgpu_forward_v4 / _v6)
+FWD_LXC, FWD_NETDEV = 0, 1
+FWD_ENCAP = 1
+FWD_NONE, FWD_DROP, FWD_PROXY, FWD_LOCAL, FWD_HOST, FWD_OVERLAY, FWD_STACK, FWD_TIME_EXCEEDED = range(8)
+DROP_INVALID = -134
+TUNNEL_ENDPOINT_MAP_SIZE = 65536  # bpf/node_config.h:54
+
+
+def mac_u64(mac: bytes | int) -> int:
+    """A 6-byte MAC as the __u64 the datapath stores (pkg/maps/lxcmap MAC.Uint64:
+    byte i at bits 8 i)."""
+    return mac if isinstance(mac, int) else int.from_bytes(bytes(mac)[:6], "little")
+
+
+def endpoint_info(ifindex: int = 0, lxc_id: int = 0, flags: int = 0, mac: bytes | int = 0,
+                  node_mac: bytes | int = 0) -> np.ndarray:
+    v = np.zeros((), ENDPOINT_INFO)
+    v["ifindex"], v["lxc_id"], v["flags"] = ifindex, lxc_id, flags
+    v["mac"], v["node_mac"] = mac_u64(mac), mac_u64(node_mac)
+    return v
+
+
 def get_prefix_mask_be(prefix: int) -> int:
     """GET_PREFIX (bpf/lib/ipv6.h:136-138): network-order mask of `prefix` bits."""
     if prefix <= 0:

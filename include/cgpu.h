@@ -320,6 +320,53 @@ int cgpu_endpoint_update(cgpu_ctx *ctx, const cgpu_endpoint_key *key, uint64_t f
 int cgpu_endpoint_delete(cgpu_ctx *ctx, const cgpu_endpoint_key *key);
 int cgpu_endpoint_lookup(cgpu_ctx *ctx, const cgpu_endpoint_key *key);
 
+/* The value of cilium_lxc, struct endpoint_info (bpf/lib/common.h:165-173,
+ * 48 B; mac_t is __u64): what the forwarding step (cgpu_forward_v4 / _v6)
+ * reads of a local endpoint.  The Go writer: pkg/maps/lxcmap/lxcmap.go:94-113. */
+#define CGPU_ENDPOINT_F_HOST 1u /* ENDPOINT_F_HOST: the local host itself */
+typedef struct cgpu_endpoint_info {
+	uint32_t ifindex;
+	uint16_t unused;
+	uint16_t lxc_id;
+	uint32_t flags;
+	uint32_t pad0_;    /* the C layout's hole before the first __u64 */
+	uint64_t mac;
+	uint64_t node_mac;
+	uint32_t pad[4];
+} cgpu_endpoint_info;
+#if defined(__cplusplus)
+static_assert(sizeof(cgpu_endpoint_info) == 48, "struct endpoint_info is 48 bytes");
+#else
+_Static_assert(sizeof(cgpu_endpoint_info) == 48, "struct endpoint_info is 48 bytes");
+#endif
+/* cgpu_endpoint_update with a value (cgpu_endpoint_update itself writes an
+ * all-zero one, also over an existing value; cgpu_endpoint_delete removes key
+ * and value).  Same flags, errno and endpoints_max.  lookup_info: the stored
+ * 48 bytes (the MACs included, for a caller that rewrites frames), -ENOENT. */
+int cgpu_endpoint_update_info(cgpu_ctx *ctx, const cgpu_endpoint_key *key,
+			      const cgpu_endpoint_info *info, uint64_t flags);
+int cgpu_endpoint_lookup_info(cgpu_ctx *ctx, const cgpu_endpoint_key *key,
+			      cgpu_endpoint_info *info_out);
+
+/* ------------------------------------------------------------------ */
+/* tunnel map cilium_tunnel_map (bpf/lib/maps.h:92-101,                 */
+/* pkg/maps/tunnel/tunnel.go): prefix -> node, key and value both a raw */
+/* 20-byte endpoint_key                                                 */
+/* ------------------------------------------------------------------ */
+/* A hash map compared on the whole 20-byte key (pad bytes and family
+ * included); CGPU_ANY / NOEXIST / EXIST, -ENOENT, -E2BIG at
+ * CGPU_TUNNEL_MAP_SIZE entries (TUNNEL_ENDPOINT_MAP_SIZE, bpf/node_config.h:54).
+ * get_next_key (NULL = first) walks the keys in byte order.  Works on a
+ * host-only context; reaches the device at cgpu_commit.  The datapath reads
+ * only the first four bytes of a value (tunnel->ip4, bpf/lib/encap.h:59). */
+#define CGPU_TUNNEL_MAP_SIZE 65536u
+int cgpu_tunnel_update(cgpu_ctx *ctx, const cgpu_endpoint_key *key, const cgpu_endpoint_key *val,
+		       uint64_t flags);
+int cgpu_tunnel_delete(cgpu_ctx *ctx, const cgpu_endpoint_key *key);
+int cgpu_tunnel_lookup(cgpu_ctx *ctx, const cgpu_endpoint_key *key, cgpu_endpoint_key *val_out);
+int cgpu_tunnel_get_next_key(cgpu_ctx *ctx, const cgpu_endpoint_key *key, cgpu_endpoint_key *next_out);
+size_t cgpu_tunnel_count(cgpu_ctx *ctx);
+
 /* ------------------------------------------------------------------ */
 /* service map cilium_lb4_services: pkg/maps/lbmap (UpdateService /     */
 /* DeleteService, lbmap.go:341-429), bpf/lib/lb.h:70-76                  */
@@ -648,7 +695,8 @@ int cgpu_classify_v6_lb(cgpu_ctx *ctx, const cgpu_tuples_v6 *t, const uint16_t *
  *   service drop, stage 8 XDP drop).  With the service step the address
  *   looked up is the one the identity is looked up on, the daddr after
  *   translation.  The value does not depend on the policy verdict: the
- *   consumer decides about encapsulation.  Every element is written.
+ *   consumer decides about encapsulation (cgpu_forward_v4 / _v6 take this
+ *   column as their `tunnel` input).  Every element is written.
  * tunnel == NULL: exactly the call `path` names.  -ENODEV on a host-only
  * context; -EINVAL for a bad path, or a non-NULL tunnel on a context without
  * cgpu_config.ipcache_tunnel.
@@ -1291,6 +1339,97 @@ typedef struct cgpu_mapstate_stats {
 int cgpu_mapstate_sync(cgpu_ctx *ctx, const cgpu_l3_program *prog, const cgpu_label_sets *endpoints,
 		       const cgpu_label_sets *identities, const cgpu_mapstate_spec *spec,
 		       cgpu_mapstate_stats *stats);
+
+/* ------------------------------------------------------------------ */
+/* forwarding decision of allowed packets                               */
+/* ------------------------------------------------------------------ */
+/*
+ * Where a packet goes once a classify call allowed it: the rest of
+ * handle_ipv4_from_lxc / ipv6_l3_from_lxc (bpf_lxc.c:547-657, :242-354,
+ * CGPU_FWD_LXC) and of the netdev's handle_ipv4 / handle_ipv6
+ * (bpf_netdev.c:422-452, :240-274, CGPU_FWD_NETDEV).  A call of its own, run
+ * after a classify call on columns the caller already has; it walks no
+ * ipcache and touches no counter, metric or conntrack entry.
+ *
+ * CGPU_FWD_LXC, per packet in this order:
+ *   1. no CGPU_F_EGRESS: NONE, all outputs 0 (the to-container program's
+ *      delivery is the redirect a LOCAL result already stands for);
+ *   2. verdict < 0: DROP, ret = verdict;
+ *   3. verdict > 0: PROXY, arg = verdict, ifindex = host_ifindex      [ttl]
+ *   4. cilium_lxc holds daddr: with ENDPOINT_F_HOST HOST, ifindex =
+ *      host_ifindex; else LOCAL, ifindex = ep->ifindex, arg = lxc_id   [ttl]
+ *   5. CGPU_FWD_ENCAP: tunnel != 0: OVERLAY, arg = tunnel, ifindex =
+ *      encap_ifindex; else a cilium_tunnel_map hit on {daddr & ipv4_mask} /
+ *      {daddr / 96}: OVERLAY, arg = the value's ip4 word;
+ *   6. STACK                                                           [ttl]
+ * CGPU_FWD_NETDEV (verdict and flags are not read):
+ *   1. cilium_lxc holds daddr: with ENDPOINT_F_HOST STACK, else LOCAL  [ttl]
+ *   2. CGPU_FWD_ENCAP: tunnel != 0: OVERLAY; else, only where (daddr &
+ *      ipv4_cluster_mask) == ipv4_cluster_range (IPv6: daddr's first 96 bits
+ *      are ROUTER_IP's), the tunnel map as above;
+ *   3. STACK.
+ * [ttl]: the branch calls ipv4_l3 / ipv6_l3, so a packet with ttl <= 1 ends
+ * there instead: IPv4 DROP with ret CGPU_DROP_INVALID (lib/l3.h:57-60), IPv6
+ * TIME_EXCEEDED with the other outputs 0 (lib/l3.h:36-43).  Encapsulation
+ * does not decrement.  The MAC rewrite, the decrement itself and checksums
+ * are packet rewriting and not done here.
+ */
+#define CGPU_FWD_LXC 0u
+#define CGPU_FWD_NETDEV 1u
+#define CGPU_FWD_ENCAP 1u /* cgpu_fwd_params.flags: the ENCAP_IFINDEX build */
+
+#define CGPU_FWD_NONE 0
+#define CGPU_FWD_DROP 1
+#define CGPU_FWD_PROXY 2
+#define CGPU_FWD_LOCAL 3
+#define CGPU_FWD_HOST 4
+#define CGPU_FWD_OVERLAY 5
+#define CGPU_FWD_STACK 6
+#define CGPU_FWD_TIME_EXCEEDED 7
+#define CGPU_DROP_INVALID (-134) /* DROP_INVALID, bpf/lib/common.h */
+
+typedef struct cgpu_fwd_params {
+	uint32_t mode;          /* CGPU_FWD_LXC | CGPU_FWD_NETDEV */
+	uint32_t flags;         /* CGPU_FWD_ENCAP */
+	uint32_t ipv4_mask;     /* IPV4_MASK (node_config.h:41), raw u32 as compared with daddr */
+	uint32_t host_ifindex;  /* HOST_IFINDEX */
+	uint32_t encap_ifindex; /* ENCAP_IFINDEX */
+	uint32_t reserved[3];   /* must be 0 (-EINVAL) */
+} cgpu_fwd_params;
+
+typedef struct cgpu_fwd_in {
+	const void *daddr;      /* v4: u32 per packet; v6: 16 bytes, any alignment; the
+				   packet's daddr as it leaves the classify step */
+	const int32_t *verdict; /* the classify call's verdict; NULL only in NETDEV mode */
+	const uint32_t *tunnel; /* raw tunnel_endpoint word per packet; NULL = all 0 */
+	const uint8_t *flags;   /* CGPU_F_EGRESS; NULL only in NETDEV mode */
+	const uint8_t *ttl;     /* IPv4 ttl / IPv6 hop_limit; NULL = never expired */
+} cgpu_fwd_in;
+
+/* all device pointers; any output but action may be NULL; every element of a
+ * given column is written */
+typedef struct cgpu_fwd_out {
+	uint8_t *action;   /* CGPU_FWD_* */
+	int32_t *ret;      /* the DROP_* code of a DROP, else 0 */
+	uint32_t *ifindex;
+	uint32_t *arg;     /* PROXY: proxy port; LOCAL: lxc_id; OVERLAY: tunnel endpoint */
+} cgpu_fwd_out;
+
+/* The tunnel column is the one the caller has: the `tunnel` output of a
+ * _tun / _ct_tun call in LXC mode, of cgpu_ipcache_lookup_v4 / _v6 in NETDEV
+ * mode.  -ENODEV on a host-only context; -EINVAL for a null required column,
+ * a bad mode, unknown flag bits, nonzero reserved words or a misaligned
+ * 4-byte column. */
+int cgpu_forward_v4(cgpu_ctx *ctx, const cgpu_fwd_params *params, const cgpu_fwd_in *in, size_t n,
+		    const cgpu_fwd_out *out, void *stream);
+int cgpu_forward_v6(cgpu_ctx *ctx, const cgpu_fwd_params *params, const cgpu_fwd_in *in, size_t n,
+		    const cgpu_fwd_out *out, void *stream);
+/* Device bytes of the published snapshot's forwarding tables: out[0..3] =
+ * IPv4 endpoints, IPv6 endpoints, IPv4 tunnel map, IPv6 tunnel map.  They are
+ * built only while some endpoint has a non-zero value or the tunnel map holds
+ * a key (all 0 otherwise: the snapshot's endpoint sets answer), and are no
+ * part of cgpu_table_bytes, cgpu_table_verify or the upload check. */
+int cgpu_forward_table_bytes(cgpu_ctx *ctx, uint64_t *out);
 
 /* ------------------------------------------------------------------ */
 /* counters                                                             */
