@@ -5230,9 +5230,6 @@ CGPU_EXPORT int cgpu_forward_table_bytes(cgpu_ctx *c, uint64_t *out)
 #ifndef CGPU_HS_UP_DMA_BELOW
 #define CGPU_HS_UP_DMA_BELOW 64
 #endif
-#ifndef CGPU_HS_STORE
-#define CGPU_HS_STORE 1
-#endif
 
 /* a host batch: its input and output columns and their bytes per tuple */
 struct hs_cols {
@@ -5391,7 +5388,7 @@ static int host_pipeline(cgpu_ctx *c, size_t n, const hs_cols &C, hipStream_t cs
 			void *dd = dst_mapped ? dst_mapped[col] : dst[col];
 			const void *ss = src_mapped ? src_mapped[col] : src[col];
 			const bool by_cu = kind == hipMemcpyDeviceToHost || !dma_up;
-			if (CGPU_HS_STORE && by_cu && dd && ss && aligned(dd) && aligned(ss)) {
+			if (by_cu && dd && ss && aligned(dd) && aligned(ss)) {
 				which[d.n] = col;
 				d.seg[d.n++] = copy_seg{dd, ss, bytes[col]};
 				continue;

@@ -1154,10 +1154,6 @@ struct cls_args {
  *   policy : policy.h:46-110, negative collapsed to DROP_POLICY
  * v: verdict; id: label given to policy; st: 1 exact, 2 L3-only, 3 wildcard,
  * 0 miss; ctr: the hit entry's counter slot or -1. */
-#ifndef CGPU_POLICY_Q_PROBES
-#define CGPU_POLICY_Q_PROBES 0
-#endif
-
 struct decision {
 	int32_t v;
 	uint32_t id, st;
@@ -1228,32 +1224,21 @@ __device__ __forceinline__ decision decide(const cgpu_snapshot &s, bool egress, 
 	uint32_t z = 0;
 	int ctr = -1;
 	d.st = 0;
-	if (CGPU_POLICY_Q_PROBES) {
-		if (!frag) {
-			ctr = pol_lookup(s.pol, d.id, hi4, ep, &z);
-			d.st = 1;
-		}
-		if (ctr < 0) {
-			ctr = pol_lookup(s.pol, d.id, eg, ep, &z);
-			d.st = 2;
-		}
-	} else {
-		/* as policy_q: the {identity, endpoint, direction} group slot gives
-		 * probe 2 and the bloom that gates probe 1 */
-		const uint32_t ed = ep | (egress ? 1u << 16 : 0u);
-		const uint32_t bg = pg_hash(d.id, ed) & s.pg.mask;
-		const uint4 grp = pg_resolve(s.pg, s.pg.slots[bg], bg, d.id, ed);
-		const uint32_t bl = pg_bloom(dport, proto);
-		if (!frag && (grp.w & bl) == bl) {
-			ctr = pol_lookup(s.pol, d.id, hi4, ep, &z);
-			d.st = 1;
-		}
-		if (ctr < 0) {
-			d.st = 2;
-			if ((grp.z & POL_CTR_MASK) != POL_CTR_EMPTY) {
-				ctr = (int)(grp.z & POL_CTR_MASK);
-				z = 0;
-			}
+	/* as policy_q: the {identity, endpoint, direction} group slot gives
+	 * probe 2 and the bloom that gates probe 1 */
+	const uint32_t ed = ep | (egress ? 1u << 16 : 0u);
+	const uint32_t bg = pg_hash(d.id, ed) & s.pg.mask;
+	const uint4 grp = pg_resolve(s.pg, s.pg.slots[bg], bg, d.id, ed);
+	const uint32_t bl = pg_bloom(dport, proto);
+	if (!frag && (grp.w & bl) == bl) {
+		ctr = pol_lookup(s.pol, d.id, hi4, ep, &z);
+		d.st = 1;
+	}
+	if (ctr < 0) {
+		d.st = 2;
+		if ((grp.z & POL_CTR_MASK) != POL_CTR_EMPTY) {
+			ctr = (int)(grp.z & POL_CTR_MASK);
+			z = 0;
 		}
 	}
 	if (ctr < 0 && !frag) {
@@ -1280,7 +1265,7 @@ __device__ __forceinline__ decision decide(const cgpu_snapshot &s, bool egress, 
  * key can exist; probe 3 gathers directly.  Same results as the three
  * probes in order (GROUP false: the probes themselves, for kernels at their
  * register limit - the group slots' registers spill k_ct_finish, 2.18 ->
- * 2.36 ms, profiles/r4_i/; CGPU_POLICY_Q_PROBES: every caller, A/B). */
+ * 2.36 ms, profiles/r4_i/). */
 template <int Q, bool GROUP = true>
 __device__ __forceinline__ void policy_q(const cgpu_snapshot &s, const bool (&act)[Q], const bool (&eg)[Q],
 					 const bool (&frag)[Q], const uint32_t (&dport)[Q], const uint32_t (&proto)[Q],
@@ -1299,7 +1284,7 @@ __device__ __forceinline__ void policy_q(const cgpu_snapshot &s, const bool (&ac
 		ctr[u] = -1;
 		d[u].st = 0;
 	}
-	if (CGPU_POLICY_Q_PROBES || !GROUP) {
+	if (!GROUP) {
 		/* probe 1: {id, dport, proto, dir} (not for fragments) */
 #pragma unroll
 		for (int u = 0; u < Q; u++) {
@@ -1709,21 +1694,9 @@ __host__ __device__ __forceinline__ uint32_t v6t_lds_bloom(const v6_lpm &t)
 	return t.root && t.bl64 && t.bl64_mask < V6T_BLOOM_MAX_WORDS ? t.bl64_mask + 1u : 0u;
 }
 
-/* 1: the x4 lookups read a node's whole 128-B line (boundaries, outer AND
- * the 16 region labels) in one go and select the label in registers, so a
- * lookup has no dependent label load; 0: the 64-B
- * boundary half, then the label word */
-#ifndef CGPU_V6T_FULL_LINE
-#define CGPU_V6T_FULL_LINE 0
-#endif
-
-__device__ __forceinline__ uint32_t sel16(const uint4 &a, const uint4 &b, const uint4 &c, const uint4 &d, uint32_t i)
-{
-	const uint4 v = (i & 8u) ? ((i & 4u) ? d : c) : ((i & 4u) ? b : a);
-	const uint32_t lo = (i & 1u) ? v.y : v.x, hi = (i & 1u) ? v.w : v.z;
-	return (i & 2u) ? hi : lo;
-}
-
+/* The x4 lookups read the 64-B boundary half of a node's line, then the
+ * label word (the whole 128-B line in one go, the label selected in
+ * registers, measured 4.68 against 2.86 ms: profiles/r5_d/ab_v6.log) */
 /* bl: the /64 bloom staged in LDS (v6_lpm.bl64), or NULL: probe h64 for
  * every tuple under a deep /32 */
 template <int Q>
@@ -1787,8 +1760,6 @@ __device__ __forceinline__ void v6t_lookup_q(const v6_lpm &t, const uint32_t *ld
 	bool node[Q], deep[Q], out[Q];
 	uint32_t line[Q], home[Q];
 	uint4 q0[Q], q1[Q], q2[Q], q3[Q], h0[Q], h1[Q];
-	constexpr bool FULL = CGPU_V6T_FULL_LINE && V6T_NB == 15u;
-	uint4 q4[FULL ? Q : 1], q5[FULL ? Q : 1], q6[FULL ? Q : 1], q7[FULL ? Q : 1];
 #pragma unroll
 	for (int u = 0; u < Q; u++) {
 		node[u] = b32i[u] != 0xFFFFFFFFu && (n[u].x & DIR_TAG_MASK) == DIR_TAG_GROUP;
@@ -1811,20 +1782,12 @@ __device__ __forceinline__ void v6t_lookup_q(const v6_lpm &t, const uint32_t *ld
 #pragma unroll
 	for (int u = 0; u < Q; u++) {
 		q0[u] = q1[u] = q2[u] = q3[u] = h0[u] = h1[u] = make_uint4(0, 0, 0, 0);
-		if constexpr (FULL)
-			q4[u] = q5[u] = q6[u] = q7[u] = make_uint4(0, 0, 0, 0);
 		if (node[u]) {
 			const uint4 *q = reinterpret_cast<const uint4 *>(t.pool) + (V6T_LW / 4u) * line[u];
 			q0[u] = q[0];
 			q1[u] = q[1];
 			q2[u] = q[2];
 			q3[u] = q[3];
-			if constexpr (FULL) {
-				q4[u] = q[4];
-				q5[u] = q[5];
-				q6[u] = q[6];
-				q7[u] = q[7];
-			}
 		}
 		if (deep[u]) {
 			h0[u] = t.h64[2u * home[u]];
@@ -1839,13 +1802,6 @@ __device__ __forceinline__ void v6t_lookup_q(const v6_lpm &t, const uint32_t *ld
 			continue;
 		if (((n[u].y >> 5) & 7u) == V6T_LONG) {
 			lab[u] = v6t_long(t.pool, line[u], q0[u].x, w[u].y);
-		} else if constexpr (FULL) {
-			const uint32_t x = w[u].y;
-			const uint32_t c = (q0[u].x < x) + (q0[u].y < x) + (q0[u].z < x) + (q0[u].w < x) +
-					   (q1[u].x < x) + (q1[u].y < x) + (q1[u].z < x) + (q1[u].w < x) +
-					   (q2[u].x < x) + (q2[u].y < x) + (q2[u].z < x) + (q2[u].w < x) +
-					   (q3[u].x < x) + (q3[u].y < x) + (q3[u].z < x);
-			lab[u] = out[u] ? q3[u].w : sel16(q4[u], q5[u], q6[u], q7[u], c);
 		} else {
 			lab[u] = v6t_label(t.pool, line[u], out[u], q0[u], q1[u], q2[u], q3[u], w[u].y);
 		}
@@ -1915,20 +1871,14 @@ struct ftuple {
 /* the x4 schedule's cold-slot atomics of a full quad go out behind the next
  * quad's column loads: config 2 1.612 -> 1.592 ms, v6 2.688 -> 2.661
  * (deferring the output stores as well: 2.08 ms, spills; profiles/r6_n/) */
-#ifndef CGPU_X4_DEFER_COLD
-#define CGPU_X4_DEFER_COLD 1
-#endif
 #ifndef CGPU_FF_H
 #define CGPU_FF_H 2 /* fused frames: slots loaded together (1, 2, 4) */
 #endif
 #define FF_H CGPU_FF_H
-#ifndef CGPU_FF_STAGE
-#define CGPU_FF_STAGE 1 /* fused frames: coalesced tile loads handed out through LDS */
-#endif
 /* fused frames' LDS rows per wave: 64 slots x 80 B */
 #define FF_STG_U4 320u
-/* fused frames: staging buffers shared by a workgroup's 16 waves (0: one
- * per wave) */
+/* fused frames: staging buffers shared by a workgroup's 16 waves (one per
+ * wave measured 2.60 against 2.52 ms: profiles/r5_l/ab_frames_pool.log) */
 #ifndef CGPU_FF_POOL
 #define CGPU_FF_POOL 4
 #endif
@@ -2006,7 +1956,6 @@ __global__ __launch_bounds__(NT, MINW) void k_classify_x4(cgpu_snapshot s, cls_a
 	int16_t *fst = reinterpret_cast<int16_t *>(lxl + (FF ? 2u * FR_LXC_LDS : 0u));
 	/* fused frames: this wave's staging rows, after the statuses */
 	uint4 *stg0 = reinterpret_cast<uint4 *>(fst + (FF ? NT * Q : 0));
-#if CGPU_FF_POOL
 	/* CGPU_FF_POOL staging buffers shared by the workgroup's waves (a wave
 	 * holds one only between its tile's LDS write and read), then their
 	 * busy flags: the LDS the per-wave rows took goes to hot counter slots */
@@ -2014,9 +1963,6 @@ __global__ __launch_bounds__(NT, MINW) void k_classify_x4(cgpu_snapshot s, cls_a
 	if (FF && threadIdx.x < CGPU_FF_POOL)
 		pool_busy[threadIdx.x] = 0u;
 	uint4 *stg = stg0;
-#else
-	uint4 *stg = stg0 + (threadIdx.x >> 6) * FF_STG_U4;
-#endif
 	if constexpr (FF) {
 		for (uint32_t k = threadIdx.x; k < 2u * s.n_lxc; k += NT)
 			lxl[k] = s.lxc[k];
@@ -2044,10 +1990,10 @@ __global__ __launch_bounds__(NT, MINW) void k_classify_x4(cgpu_snapshot s, cls_a
 	__syncthreads();
 
 	const uint32_t lane = threadIdx.x & 63u;
-	/* CGPU_X4_DEFER_COLD: a quad's cold-slot atomics (into pk) are issued
+	/* DEFER: a quad's cold-slot atomics (into pk) are issued
 	 * after the next quad's column loads, so the wait for those loads does
 	 * not wait for them too (vmcnt retires in issue order) */
-	constexpr bool DEFER = CGPU_X4_DEFER_COLD && !FF && Q == 4;
+	constexpr bool DEFER = !FF && Q == 4;
 	uint32_t dcs[DEFER ? Q : 1], dln[DEFER ? Q : 1];
 #pragma unroll
 	for (int u = 0; u < (DEFER ? Q : 1); u++)
@@ -2108,7 +2054,6 @@ __global__ __launch_bounds__(NT, MINW) void k_classify_x4(cgpu_snapshot s, cls_a
 					if (u % FF_H == 0) {
 #pragma unroll
 						for (int h = 0; h < FF_H; h++) {
-#if CGPU_FF_STAGE
 							/* the wave's tile of 64 slots as four coalesced
 							 * 1-KiB loads: load k, lane l = slot 16 k + l / 4,
 							 * quarter l % 4 */
@@ -2118,18 +2063,9 @@ __global__ __launch_bounds__(NT, MINW) void k_classify_x4(cgpu_snapshot s, cls_a
 								raw[h][k] = t + 16u * k + (lane >> 2) < a.n
 										    ? ld_x4<NTL>(fd + t * 64u + 1024u * k + 16u * lane)
 										    : make_uint4(0, 0, 0, 0);
-#else
-							const bool okh = iu(u + h) < a.n;
-							const uint64_t ih = okh ? iu(u + h) : i0;
-#pragma unroll
-							for (int k = 0; k < 4; k++)
-								raw[h][k] = okh ? ld_x4<NTL>(fd + ih * 64u + 16u * k) : make_uint4(0, 0, 0, 0);
-#endif
 						}
 					}
 					fwin W;
-#if CGPU_FF_STAGE
-#if CGPU_FF_POOL
 					/* take a free staging buffer (lane 0 for the wave) */
 					uint32_t pb = 0;
 					if (lane == 0) {
@@ -2152,7 +2088,6 @@ __global__ __launch_bounds__(NT, MINW) void k_classify_x4(cgpu_snapshot s, cls_a
 					}
 					pb = (uint32_t)__shfl((int)pb, 0, 64);
 					stg = stg0 + pb * FF_STG_U4;
-#endif
 					/* each lane's slot through the wave's LDS rows (64 slots of
 					 * 80 B: conflict-free 16-B reads) */
 #pragma unroll
@@ -2168,20 +2103,9 @@ __global__ __launch_bounds__(NT, MINW) void k_classify_x4(cgpu_snapshot s, cls_a
 						W.w[4 * q + 3] = v.w;
 					}
 					__builtin_amdgcn_wave_barrier();
-#if CGPU_FF_POOL
 					/* the reads above are done before the buffer is free */
 					if (lane == 0)
 						__hip_atomic_store(&pool_busy[pb], 0u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-#endif
-#else
-#pragma unroll
-					for (int k = 0; k < 4; k++) {
-						W.w[4 * k] = raw[u % FF_H][k].x;
-						W.w[4 * k + 1] = raw[u % FF_H][k].y;
-						W.w[4 * k + 2] = raw[u % FF_H][k].z;
-						W.w[4 * k + 3] = raw[u % FF_H][k].w;
-					}
-#endif
 					const bool egress = flv[u] & 1u;
 					const ftuple t = parse_frame_w(s, W, fd + i * 64u, len[u], min(len[u], 64u), egress, ep[u], lxl);
 					const bool v6 = t.status == 0 && t.fam != 4u;
@@ -3566,11 +3490,6 @@ __device__ __forceinline__ void cover6_any_q(const cover6 &t, const uint32_t *ld
 	}
 }
 
-#ifdef CGPU_DIAG_PF6_PREFETCH /* timing-only tool build (tools/diag_ab.py) */
-#define PF6_PREFETCH true
-#else
-#define PF6_PREFETCH false /* measured slower: the extra registers spill (r2) */
-#endif
 #ifdef CGPU_DIAG_PF6_Q /* timing-only tool build: packets per lane */
 #define PF6_Q CGPU_DIAG_PF6_Q
 #else
@@ -3607,10 +3526,6 @@ __global__ __launch_bounds__(NT) void k_prefilter_v6_q(cgpu_snapshot s, prefilte
 	/* wave-step g covers packets [g * Q, g * Q + 64 Q): packet u of a lane
 	 * is g * Q + 64 u + lane, so each column load of a wave reads 64
 	 * consecutive packets (1 KiB of addresses, 64 B of flags) */
-	/* PF6_PREFETCH: the source addresses and flags of the wave's next step
-	 * are loaded while this one resolves */
-	uint4 nsa[Q];
-	uint32_t nf[Q];
 	auto load_src = [&](uint64_t g, uint4 (&sa)[Q], uint32_t (&f)[Q]) {
 #pragma unroll
 		for (int u = 0; u < Q; u++) {
@@ -3621,24 +3536,12 @@ __global__ __launch_bounds__(NT) void k_prefilter_v6_q(cgpu_snapshot s, prefilte
 		}
 	};
 	const uint64_t g0 = (uint64_t)blockIdx.x * NT + threadIdx.x - lane;
-	if (PF6_PREFETCH && g0 * Q < a.n)
-		load_src(g0, nsa, nf);
 	for (uint64_t g = g0; g * Q < a.n; g += T) {
 		uint4 sa[Q], da[Q];
 		uint32_t f[Q];
 		uint64_t ix[Q];
 		bool act[Q], hit[Q];
-		if (PF6_PREFETCH) {
-#pragma unroll
-			for (int u = 0; u < Q; u++) {
-				sa[u] = nsa[u];
-				f[u] = nf[u];
-			}
-			if ((g + T) * Q < a.n)
-				load_src(g + T, nsa, nf);
-		} else {
-			load_src(g, sa, f);
-		}
+		load_src(g, sa, f);
 #pragma unroll
 		for (int u = 0; u < Q; u++)
 			ix[u] = g * Q + 64u * u + lane;
@@ -4052,9 +3955,6 @@ static cgpu_snapshot with_lds_hot(const cgpu_snapshot &s, size_t max_hot)
 #ifndef CGPU_IPC6_MINW
 #define CGPU_IPC6_MINW 1 /* workgroups per CU the register budget aims at */
 #endif
-#ifndef CGPU_IPC6_SPEC
-#define CGPU_IPC6_SPEC 1 /* addresses loaded beside the direction flag (0: behind it) */
-#endif
 /* svc_out[i].x: SVC_* | LBS_* << 8 | slave << 16; .y target; .z the dport
  * rewrite (0 none) | rev_nat_index << 16 */
 #define SVC_NONE 0u
@@ -4091,7 +3991,6 @@ __global__ __launch_bounds__(NT, CGPU_IPC6_MINW) void k_ipc6_pre(cgpu_snapshot s
 		uint4 w[Q];
 		bool act[Q], eg[Q];
 		uint32_t e[Q];
-#if CGPU_IPC6_SPEC
 		/* both addresses (and the service outcome) are loaded with the
 		 * direction flag, not behind it: one round trip less per tuple for
 		 * 16 more bytes of stream (k_ipc6_pre 1.62 ms, round 5) */
@@ -4116,22 +4015,6 @@ __global__ __launch_bounds__(NT, CGPU_IPC6_MINW) void k_ipc6_pre(cgpu_snapshot s
 				x = st[u];
 			w[u] = act[u] ? v6_host_words(x) : make_uint4(0, 0, 0, 0);
 		}
-#else
-#pragma unroll
-		for (int u = 0; u < Q; u++) {
-			const uint64_t i = g + (uint64_t)u * T;
-			act[u] = i < n;
-			w[u] = make_uint4(0, 0, 0, 0);
-			eg[u] = false;
-			if (act[u]) {
-				eg[u] = flags[i] & 1u;
-				uint4 x = ld_x4<true>((eg[u] ? da : sa) + i);
-				if (svc && eg[u] && (svc[2u * i].x & 3u) == SVC_XLATED)
-					x = svc[2u * i + 1u];
-				w[u] = v6_host_words(x);
-			}
-		}
-#endif
 		uint32_t te[TUN ? Q : 1];
 		bool twant[TUN ? Q : 1];
 		if constexpr (TUN) {
@@ -4226,8 +4109,7 @@ static hipError_t launch_x4(const cgpu_snapshot &s0, const cls_args &a, hipStrea
 	fixed = (fixed + 7u) & ~(size_t)7u;
 	/* fused frames: the endpoint rows (+ alignment) and 4 statuses per lane */
 	const size_t ff = FF ? 16u + 2u * FR_LXC_LDS * 16u + (size_t)NT * 4u * 2u +
-				       (CGPU_FF_STAGE ? (size_t)(CGPU_FF_POOL ? CGPU_FF_POOL : NT / 64) * FF_STG_U4 * 16u + 64u
-						      : 0u)
+				       (size_t)CGPU_FF_POOL * FF_STG_U4 * 16u + 64u
 			     : 0u;
 	fixed += ff;
 	const cgpu_snapshot s = with_lds_hot(s0, fixed < X4_LDS_BUDGET ? (X4_LDS_BUDGET - fixed) / 8u : 0u);
@@ -4687,7 +4569,7 @@ hipError_t launch_classify_frames_x4(const cgpu_snapshot &s, const frames_args &
 		/* fused: the classify kernel parses the slots itself (no tuple
 		 * columns written and re-read), the IPv6 frames as below.  Each
 		 * wave reads its 64-slot tile as four coalesced 1-KiB loads and
-		 * hands the slots out through LDS (CGPU_FF_STAGE): 2.64 against
+		 * hands the slots out through LDS: 2.64 against
 		 * 2.81 ms per 64M frames for the two passes, 2.96 with per-lane
 		 * slot loads (profiles/r5_j/) */
 		cls_args f4{a.data, nullptr, nullptr, nullptr, a.flags, a.len, a.ep, a.verdict, a.identity, a.stage,
@@ -4945,35 +4827,10 @@ hipError_t launch_slot_init(uint64_t *totals, uint64_t *delta, const uint32_t *s
 #ifndef CGPU_CT_FNT
 #define CGPU_CT_FNT 1024
 #endif
-/* phase 2b groups an address entry no phase-2 packet can read by its whole
- * key (k_ct_owed_bloom); 0: by its pair (A/B) */
-#ifndef CGPU_OWED_BY_KEY
-#define CGPU_OWED_BY_KEY 1
-#endif
-/* the service paths' forward decisions: 0 inside the per-packet prep, 1 a
- * k_ct_decq pass after it (Q packets per lane).  Measured slower (ctlb
- * 25.19 -> 25.53 ms, ctlb6 24.13 -> 26.93: the v6 pass stages the trie
- * levels in LDS per 256-thread workgroup, profiles/r4_o/): kept for A/B */
-#ifndef CGPU_CT_SVC_DECQ
-#define CGPU_CT_SVC_DECQ 0
-#endif
-/* the service path's prep: Q packets per lane (k_ct_prep_svc_q), 1 = the
- * per-lane k_ct_prep */
+/* the service path's prep: Q packets per lane (k_ct_prep_svc_q; the per-lane
+ * k_ct_prep measured 20.61 against 20.40 ms, profiles/r5_k/ab_ctlb_svc_q.log) */
 #ifndef CGPU_CT_SVC_Q
 #define CGPU_CT_SVC_Q 2
-#endif
-/* ... IPv6 (k_ct_prep6's per-lane decide<1> walks the trie from global
- * memory: 32 GB of HBM traffic per 64M packets, profiles/r4_prof/ctlb6):
- * 1 = k_ct_decq on a resident grid of 1024-thread workgroups, the trie
- * levels staged in LDS once per CU as k_ipc6_pre.  Measured slower too,
- * 24.10 -> 24.75 ms (profiles/r4_s/): off */
-#ifndef CGPU_CT_SVC_DECQ6
-#define CGPU_CT_SVC_DECQ6 0
-#endif
-/* ... IPv6: 1 = the trie pre-pass on the translated addresses, then
- * k_ct_prep6_q<SVC> (as the plain IPv6 path) */
-#ifndef CGPU_CT_SVC_PRE6
-#define CGPU_CT_SVC_PRE6 1
 #endif
 /* the stateful service step (cgpu_classify_v4_ctlb) */
 #define CTM_PHASE2 128u   /* the packet's address pair may hold owed address entries: phase 2 */
@@ -4983,7 +4840,7 @@ hipError_t launch_slot_init(uint64_t *totals, uint64_t *delta, const uint32_t *s
 #define CTM_RELX 1024u    /* grouped by connection in phase 1: the ICMP entry a create
 			   * writes is reserved and owed to phase 2 */
 #define CT_RELP 0x20u     /* walker -> phase 2: the ICMP entry of this create is owed */
-/* Group-default results (CGPU_CT_DFLT, every conntrack path): the prep marks
+/* Group-default results (a.dflt, every conntrack path): the prep marks
  * every packet's result CT_DFLT.  A packet's orientation is a fixed function
  * of its tuple that flips for the reversed tuple and is 0 for the usual
  * initiator (ephemeral source port above the service port; an ICMP echo
@@ -4997,9 +4854,6 @@ hipError_t launch_slot_init(uint64_t *totals, uint64_t *delta, const uint32_t *s
  * most of the walker's scattered result stores with no lookup in the
  * finish (a group bitmap read there cost 0.27 ms: profiles/r6_p/, r7_a/). */
 #define CT_DFLT 0x10u
-#ifndef CGPU_CT_DFLT
-#define CGPU_CT_DFLT 1
-#endif
 /* a packet's orientation (any fixed function of its key) and its group key,
  * as k_ct_prep_q computed it (ct_conn_group over the record's tuple) */
 /* z = sport | dport << 16 (TCP / UDP ports in network order, the ICMP /
@@ -5605,7 +5459,7 @@ struct ct_args {
 	uint8_t *f2;                 /* [2n] phase-2 candidate flags (plain path) */
 	uint8_t *pcls;               /* [n] service path: phase-2 class, PCL_* (k_ct_prep) */
 	uint64_t *pk;                /* packed per-slot counters (k_ct_finish, k_unpack) */
-	uint32_t dflt; /* nonzero: group-default results (CGPU_CT_DFLT) */
+	uint32_t dflt; /* nonzero: group-default results (CT_DFLT) */
 	/* the _rnat entry points: [n] per packet, zeroed before the walks; a walker
 	 * compiled with RN stores rev_nat_index | lb_loopback << 16 of the entry a
 	 * packet hit when that index is nonzero (k_ct_rnat reads it) */
@@ -5755,7 +5609,7 @@ template <> struct ct_rec<CtK6S> {
 	}
 };
 
-/* CGPU_CT_DFLT: a walked packet's orientation from its record (ct_orient) */
+/* CT_DFLT: a walked packet's orientation from its record (ct_orient) */
 __device__ __forceinline__ bool ct6_lt(const uint4 &a, const uint4 &b)
 {
 	if (a.x != b.x)
@@ -5767,7 +5621,7 @@ __device__ __forceinline__ bool ct6_lt(const uint4 &a, const uint4 &b)
 	return a.w < b.w;
 }
 template <class K> struct ct_dflt {
-	static constexpr bool ON = CGPU_CT_DFLT != 0;
+	static constexpr bool ON = true;
 	__device__ static uint32_t orient(const ct_rec<K> &r)
 	{
 		if constexpr (K::V6 != 0) /* {daddr, saddr, {z, proto | ...}} */
@@ -5913,16 +5767,14 @@ __device__ __forceinline__ void prep4_post(const cgpu_snapshot &s, const ct_args
 			meta |= CTM_FRAG;
 		if (egress)
 			sec = ep < s.n_lxc ? s.lxc[2u * ep + 1u].w : 0u; /* SECLABEL */
-		if constexpr (!SVC || !CGPU_CT_SVC_DECQ) {
-			if (d.v >= 0) {
-				meta |= CTM_ALLOWED;
-				port = (uint32_t)d.v;
-			}
-			id = d.id;
-			if (!egress)
-				sec = d.id;
-			cst = (uint32_t)(d.ctr + 1) | (d.st << 24);
-		} /* SVC: k_ct_decq, Q packets per lane */
+		if (d.v >= 0) {
+			meta |= CTM_ALLOWED;
+			port = (uint32_t)d.v;
+		}
+		id = d.id;
+		if (!egress)
+			sec = d.id;
+		cst = (uint32_t)(d.ctr + 1) | (d.st << 24);
 	}
 	uint32_t g = ct_group(sa, da);
 	if constexpr (!SVC) {
@@ -5975,7 +5827,7 @@ __device__ __forceinline__ void prep4_post(const cgpu_snapshot &s, const ct_args
 		}
 	}
 	a.identity[i] = id;
-	if (!SERIAL && CGPU_CT_DFLT && a.dflt)
+	if (!SERIAL && a.dflt)
 		a.ct_ret[i] = CT_DFLT; /* as k_ct_prep_q */
 	uint4 *r = a.rec + RW * i;
 	r[0] = uint4{da, sa, z, pr | (tfl << 8) | (meta << 16)};
@@ -6006,13 +5858,13 @@ __global__ __launch_bounds__(256) void k_ct_prep(cgpu_snapshot s, ct_args a, boo
 		if (!prep4_pre<SVC, SERIAL>(s, a, i, p))
 			continue;
 		decision d{};
-		if (p.dec && (!SVC || !CGPU_CT_SVC_DECQ))
+		if (p.dec)
 			d = decide<0>(s, p.egress, p.frag, p.sa, p.da, uint4{}, uint4{}, p.z >> 16, p.pr, p.ep);
 		prep4_post<SVC, SERIAL>(s, a, i, p, d, conn);
 	}
 }
 
-/* k_ct_prep<true, false> (the service path) with Q packets per lane: the
+/* k_ct_prep's service path (SVC, not SERIAL) with Q packets per lane: the
  * forward decisions through decide4_q, every lookup stage's gathers of the
  * lane's packets in flight together */
 template <int Q>
@@ -6134,7 +5986,7 @@ __global__ __launch_bounds__(256) void k_ct_prep_q(cgpu_snapshot s, ct_args a, t
 				}
 			}
 			reinterpret_cast<uint16_t *>(a.f2)[i] = p2 ? 1u : 0u;
-			if (CGPU_CT_DFLT && a.dflt)
+			if (a.dflt)
 				a.ct_ret[i] = CT_DFLT; /* the walker stores only non-default results */
 			a.identity[i] = id;
 			uint4 *r = a.rec + 2u * i;
@@ -6284,7 +6136,7 @@ __global__ __launch_bounds__(256) void k_ct_prep6_q(cgpu_snapshot s, ct_args a, 
 				}
 			}
 			reinterpret_cast<uint16_t *>(a.f2)[i] = p2 ? 1u : 0u;
-			if (CGPU_CT_DFLT && a.dflt)
+			if (a.dflt)
 				a.ct_ret[i] = CT_DFLT; /* as k_ct_prep_q */
 			a.identity[i] = id;
 			uint4 *r = a.rec + 4u * i;
@@ -6295,130 +6147,6 @@ __global__ __launch_bounds__(256) void k_ct_prep6_q(cgpu_snapshot s, ct_args a, 
 			a.gkey[i] = (m & CTM_GATED) ? ct_fmix((uint32_t)i ^ 0x5bd1e995u) : gk;
 			a.idx[i] = (uint32_t)i;
 		}
-	}
-}
-
-/* The forward tuple's decision for the service paths' records (k_ct_prep /
- * k_ct_prep6 with SVC leave it out of their per-packet lanes): Q packets per
- * lane, packet i = g + u * (threads), every lookup stage's gathers in flight
- * together (decide4_q; v6 the trie walk with its levels in LDS as
- * k_ipc6_pre, then policy_q).  Patches the record as the per-packet prep
- * writes it: CTM_ALLOWED, the proxy port, src_sec_id (ingress: the source
- * identity), the counter slot | stage, and the identity column. */
-template <class K, int Q, int NT>
-__global__ __launch_bounds__(NT) void k_ct_decq(cgpu_snapshot s, ct_args a)
-{
-	constexpr bool V6 = K::V6 != 0;
-	constexpr uint32_t RW = ct_rec<K>::RW;
-	extern __shared__ __attribute__((aligned(16))) uint32_t lt[];
-	uint32_t n24 = 0, nbl = 0;
-	uint32_t *lbl = lt;
-	if constexpr (V6) {
-		n24 = v6t_lds_b24(s.ipc6);
-		nbl = v6t_lds_bloom(s.ipc6);
-		lbl = lt + v6t_lds_words(s.ipc6);
-		if (s.ipc6.root) {
-			for (uint32_t k = threadIdx.x; k < V6T_RBITS_WORDS; k += NT)
-				lt[k] = s.ipc6.rbits[k];
-			const uint32_t *b16 = reinterpret_cast<const uint32_t *>(s.ipc6.b24_16);
-			for (uint32_t k = threadIdx.x; k < n24 * 128u; k += NT)
-				lt[V6T_RBITS_WORDS + k] = b16[k];
-			for (uint32_t k = threadIdx.x; k < nbl; k += NT)
-				lbl[k] = s.ipc6.bl64[k];
-		}
-	} else {
-		for (uint32_t k = threadIdx.x; k < s.ipc4c.n_dict; k += NT)
-			lt[k] = s.ipc4c.dict[k];
-	}
-	__syncthreads();
-	const uint64_t T = (uint64_t)gridDim.x * NT;
-	for (uint64_t g = (uint64_t)blockIdx.x * NT + threadIdx.x; g < a.n; g += T * Q) {
-		bool act[Q], eg[Q], frag[Q];
-		uint32_t sa[Q], da[Q], dp[Q], pr[Q], ep[Q];
-		uint4 w6[Q], rm[Q], rd[Q];
-		decision d[Q];
-#pragma unroll
-		for (int u = 0; u < Q; u++) {
-			const uint64_t i = g + (uint64_t)u * T;
-			const uint64_t j = i < a.n ? i : 0u;
-			const uint4 *r = a.rec + RW * j;
-			/* v4: r0 = {daddr, saddr, z, proto | meta}, r1 = {w | port, len,
-			 * sec, cst}; v6: r2 = {z, proto | meta, w | port, len}, r3 =
-			 * {sec, cst, rev_nat, svcw} */
-			rm[u] = V6 ? r[2] : r[0];
-			rd[u] = V6 ? r[3] : r[1];
-			const uint32_t meta = (V6 ? rm[u].y : rm[u].w) >> 16;
-			act[u] = i < a.n && !(meta & CTM_GATED);
-			eg[u] = meta & CTM_EGRESS;
-			frag[u] = meta & CTM_FRAG;
-			dp[u] = V6 ? rm[u].x >> 16 : rm[u].z >> 16;
-			pr[u] = (V6 ? rm[u].y : rm[u].w) & 0xFFu;
-			ep[u] = a.ep[j];
-			sa[u] = V6 ? 0u : rm[u].y;
-			da[u] = V6 ? 0u : rm[u].x;
-			w6[u] = make_uint4(0, 0, 0, 0);
-			if (V6)
-				w6[u] = v6_host_words(eg[u] ? r[0] : r[1]);
-		}
-		if constexpr (V6) {
-			/* decide<1>'s identity (bpf_lxc.c:170-187 / bpf_netdev.c:203-211) */
-			uint32_t e[Q];
-			v6t_lookup_q<Q>(s.ipc6, lt, n24 != 0u, w6, act, e, nbl ? lbl : nullptr);
-#pragma unroll
-			for (int u = 0; u < Q; u++) {
-				const uint32_t label = entry_label(s.ipc6.vals, e[u]);
-				const bool in_cluster = w6[u].x == bswap32(s.router_ip64[0]) &&
-							w6[u].y == bswap32(s.router_ip64[1]);
-				if (eg[u]) {
-					d[u].id = (e[u] && label) ? label : (in_cluster ? s.cluster_id : s.world_id);
-				} else {
-					uint32_t src = s.ingress_src_identity;
-					if (src < s.health_id && e[u] && label && label != s.cluster_id)
-						src = label;
-					d[u].id = src;
-				}
-			}
-		} else {
-			ident4_q<Q>(s, lt, act, eg, sa, da, d);
-		}
-		policy_q<Q>(s, act, eg, frag, dp, pr, ep, d);
-#pragma unroll
-		for (int u = 0; u < Q; u++) {
-			const uint64_t i = g + (uint64_t)u * T;
-			if (!act[u])
-				continue;
-			const uint32_t allowed = d[u].v >= 0 ? (CTM_ALLOWED << 16) : 0u;
-			const uint32_t port = d[u].v >= 0 ? (uint32_t)d[u].v << 16 : 0u;
-			const uint32_t cst = (uint32_t)(d[u].ctr + 1) | (d[u].st << 24);
-			uint4 *r = a.rec + RW * i;
-			if (V6) {
-				r[2] = make_uint4(rm[u].x, rm[u].y | allowed, rm[u].z | port, rm[u].w);
-				r[3] = make_uint4(eg[u] ? rd[u].x : d[u].id, cst, rd[u].z, rd[u].w);
-			} else {
-				r[0] = make_uint4(rm[u].x, rm[u].y, rm[u].z, rm[u].w | allowed);
-				r[1] = make_uint4(rd[u].x | port, rd[u].y, eg[u] ? rd[u].z : d[u].id, cst);
-			}
-			a.identity[i] = d[u].id;
-		}
-	}
-}
-
-template <class K> static void launch_ct_decq(const cgpu_snapshot &s, const ct_args &a, hipStream_t st)
-{
-	if (!(K::V6 ? CGPU_CT_SVC_DECQ6 : CGPU_CT_SVC_DECQ))
-		return;
-	if constexpr (K::V6 != 0) {
-		/* as k_ipc6_pre: the staged levels once per CU */
-		constexpr int Q = 2, NT = 1024;
-		const size_t lds = (size_t)(v6t_lds_words(s.ipc6) + v6t_lds_bloom(s.ipc6)) * 4u;
-		const unsigned res = resident_blocks((const void *)k_ct_decq<K, Q, NT>, NT, lds);
-		const unsigned g = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((a.n + Q * NT - 1) / (Q * NT), res));
-		hipLaunchKernelGGL((k_ct_decq<K, Q, NT>), dim3(g), dim3(NT), lds, st, s, a);
-	} else {
-		constexpr int Q = CGPU_CT_Q;
-		const size_t lds = (size_t)s.ipc4c.n_dict * 4u;
-		const unsigned g = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((a.n + 256 * Q - 1) / (256 * Q), 8192));
-		hipLaunchKernelGGL((k_ct_decq<K, Q, 256>), dim3(g), dim3(256), lds, st, s, a);
 	}
 }
 
@@ -6599,17 +6327,15 @@ __global__ __launch_bounds__(256) void k_ct_prep6(cgpu_snapshot s, ct_args a, tu
 		if (!(meta & CTM_GATED)) {
 			if (egress)
 				sec = ep < s.n_lxc ? s.lxc[2u * ep + 1u].w : 0u; /* SECLABEL */
-			if constexpr (!SVC || !CGPU_CT_SVC_DECQ6) {
-				const decision d = decide<1, TUN>(s, egress, false, 0u, 0u, sa, da, z >> 16, pr, ep, &ta.t, &tn);
-				if (d.v >= 0) {
-					meta |= CTM_ALLOWED;
-					port = (uint32_t)d.v;
-				}
-				id = d.id;
-				if (!egress)
-					sec = d.id;
-				cst = (uint32_t)(d.ctr + 1) | (d.st << 24);
-			} /* SVC: k_ct_decq, Q packets per lane */
+			const decision d = decide<1, TUN>(s, egress, false, 0u, 0u, sa, da, z >> 16, pr, ep, &ta.t, &tn);
+			if (d.v >= 0) {
+				meta |= CTM_ALLOWED;
+				port = (uint32_t)d.v;
+			}
+			id = d.id;
+			if (!egress)
+				sec = d.id;
+			cst = (uint32_t)(d.ctr + 1) | (d.st << 24);
 		}
 		uint32_t g = ct_group(fold6(sa.x, sa.y, sa.z, sa.w), fold6(da.x, da.y, da.z, da.w));
 		{ /* phase 1 by connection, as k_ct_prep (ct_create6 writes no address
@@ -6649,9 +6375,6 @@ __global__ __launch_bounds__(256) void k_ct_prep6(cgpu_snapshot s, ct_args a, tu
  * the cache lives in VGPRs. */
 #ifndef CTC
 #define CTC 4 /* 3 ways measured 14 % slower (more re-probes) */
-#endif
-#ifndef CGPU_CT_CREATE_LOOP
-#define CGPU_CT_CREATE_LOOP 1 /* the service step's creates through one update call site */
 #endif
 #define CTC_VALID 0x10000u
 #define CTC_NEG 0x20000u
@@ -6806,172 +6529,6 @@ __device__ __forceinline__ int ctc_get(const ct_table &T, ct_cache<K> &c, const 
 	return v;
 }
 
-/* the cache entry of k, or -1 (no probe) */
-template <class K> __device__ __forceinline__ int ctc_find(ct_cache<K> &c, const typename K::key &k)
-{
-	int hit = -1;
-	ctc_each(c, [&](ctc_ent<K> &e, int j) {
-		hit = ((K::meta(e.key) & CTC_VALID) && K::same(e.key, k)) ? j : hit;
-	});
-	return hit;
-}
-
-/* One probe chain of ct_find, advanced a slot per round so that the chains
- * of several keys have their loads in flight together.  slot: -3 not
- * probed, -2 running, -1 absent (inserts may start at ff), else found. */
-struct ct_chain {
-	uint32_t h, ff, n;
-	int slot;
-};
-
-/* s = the slot as loaded; cm = its meta word re-read at the coherence point
- * when the plain read was EMPTY (ct_find's rule) */
-template <class K>
-__device__ __forceinline__ void ct_chain_eval(const ct_table &T, const typename K::key &k, typename K::key s,
-					      uint32_t cm, ct_chain &ch)
-{
-	if (ch.slot != -2)
-		return;
-	uint32_t tag = K::meta(s) >> 16;
-	if (tag == CT_TAG_EMPTY) {
-		K::meta(s) = cm;
-		tag = cm >> 16;
-		if (tag == CT_TAG_EMPTY) {
-			ch.slot = -1;
-			if (ch.ff == 0xFFFFFFFFu)
-				ch.ff = ch.h;
-			return;
-		}
-		K::reload(T, ch.h, s);
-	}
-	if (ct_tag_holds(tag) && K::same(s, k)) {
-		ch.slot = (int)ch.h;
-		return;
-	}
-	if (tag == CT_TAG_TOMB && ch.ff == 0xFFFFFFFFu)
-		ch.ff = ch.h;
-	ch.h = (ch.h + 1u) & T.mask;
-	if (++ch.n > T.mask)
-		ch.slot = -1;
-}
-
-template <class K>
-__device__ __forceinline__ void ct_find3(const ct_table &T, const typename K::key &k0, const typename K::key &k1,
-					 const typename K::key &k2, ct_chain &c0, ct_chain &c1, ct_chain &c2,
-					 uint32_t &pend)
-{
-	ct_pend_wait(pend);
-	c0.h = K::hash(k0) & T.mask;
-	c1.h = K::hash(k1) & T.mask;
-	c2.h = K::hash(k2) & T.mask;
-	while (c0.slot == -2 || c1.slot == -2 || c2.slot == -2) {
-		typename K::key s0 = k0, s1 = k1, s2 = k2;
-		if (c0.slot == -2)
-			s0 = K::load(T, c0.h);
-		if (c1.slot == -2)
-			s1 = K::load(T, c1.h);
-		if (c2.slot == -2)
-			s2 = K::load(T, c2.h);
-		uint32_t m0 = 0, m1 = 0, m2 = 0;
-		if (c0.slot == -2 && (K::meta(s0) >> 16) == CT_TAG_EMPTY)
-			m0 = __hip_atomic_load(K::tagp(T, c0.h), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		if (c1.slot == -2 && (K::meta(s1) >> 16) == CT_TAG_EMPTY)
-			m1 = __hip_atomic_load(K::tagp(T, c1.h), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		if (c2.slot == -2 && (K::meta(s2) >> 16) == CT_TAG_EMPTY)
-			m2 = __hip_atomic_load(K::tagp(T, c2.h), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		ct_chain_eval<K>(T, k0, s0, m0, c0);
-		ct_chain_eval<K>(T, k1, s1, m1, c1);
-		ct_chain_eval<K>(T, k2, s2, m2, c2);
-	}
-}
-
-/* put probed key k (chain ch, row r) into the cache, in the next entry
- * round-robin that holds none of the wanted keys k0..k2 */
-template <class K>
-__device__ __forceinline__ void ctc_install(const ct_table &T, ct_cache<K> &c, const typename K::key &k,
-					    const ct_chain &ch, const ct_row &r, const typename K::key &k0,
-					    const typename K::key &k1, const typename K::key &k2)
-{
-	if (ch.slot == -3 || ctc_find<K>(c, k) >= 0)
-		return;
-	uint32_t keep = 0;
-	ctc_each(c, [&](ctc_ent<K> &e, int j) {
-		const bool v = K::meta(e.key) & CTC_VALID;
-		if (v && (K::same(e.key, k0) || K::same(e.key, k1) || K::same(e.key, k2)))
-			keep |= 1u << j;
-	});
-	int v = -1;
-#pragma unroll
-	for (int t = 0; t < CTC; t++) {
-		int j = (int)c.next + t;
-		j = j >= CTC ? j - CTC : j;
-		v = (v < 0 && !((keep >> j) & 1u)) ? j : v;
-	}
-	c.next = v + 1 == CTC ? 0u : (uint32_t)v + 1u;
-	uint32_t vw = 0, vp = 0;
-	ct_row vr{};
-	ctc_each(c, [&](ctc_ent<K> &e, int j) {
-		vw = j == v ? K::meta(e.key) : vw;
-		vp = j == v ? e.pos : vp;
-		vr = selrow(j == v, e.row, vr);
-	});
-	if (ctc_dirty(vw)) {
-		ct_row_store(T, vp, vr);
-		c.pend = 1;
-	}
-	typename K::key nk = k;
-	K::meta(nk) = (K::cmeta(k) & 0xFFFFu) | CTC_VALID | (ch.slot < 0 ? CTC_NEG : 0u);
-	const uint32_t np = ch.slot >= 0 ? (uint32_t)ch.slot : ch.ff;
-	ctc_each(c, [&](ctc_ent<K> &e, int j) {
-		const bool t = j == v;
-		e.key = K::sel(t, nk, e.key);
-		e.pos = t ? np : e.pos;
-		e.row = selrow(t, r, e.row);
-	});
-}
-
-/* The keys a step will need (w0..w2 select them), probed together when
- * the cache lacks them: a new connection's reply key, forward key and ICMP
- * key cost one round of loads instead of three dependent probes */
-template <class K>
-__device__ __forceinline__ void ctc_prefetch(const ct_table &T, ct_cache<K> &c, const typename K::key &k0,
-					     const typename K::key &k1, const typename K::key &k2, bool w0, bool w1,
-					     bool w2)
-{
-#ifndef CGPU_CT_PREFETCH
-	/* off: probing the step's keys together measured slower than probing
-	 * them as the step needs them (ct config 21.9 -> 18.5 ms per 64M-packet
-	 * batch, profiles/r3_ct_ab): the extra chains cost more than the latency
-	 * they overlap, and most packets need only the reply key */
-	return;
-#endif
-	ct_chain c0{0, 0xFFFFFFFFu, 0, -3}, c1 = c0, c2 = c0;
-	/* one probe per distinct key: an ICMP error's forward key IS its
-	 * related key (ports 0, RELATED set), and two cache entries of one key
-	 * would lose updates and insert it twice */
-	w1 = w1 && !(w0 && K::same(k1, k0));
-	w2 = w2 && !(w0 && K::same(k2, k0)) && !(w1 && K::same(k2, k1));
-	if (w0 && ctc_find<K>(c, k0) < 0)
-		c0.slot = -2;
-	if (w1 && ctc_find<K>(c, k1) < 0)
-		c1.slot = -2;
-	if (w2 && ctc_find<K>(c, k2) < 0)
-		c2.slot = -2;
-	if (c0.slot == -3 && c1.slot == -3 && c2.slot == -3)
-		return;
-	ct_find3<K>(T, k0, k1, k2, c0, c1, c2, c.pend);
-	ct_row r0{}, r1{}, r2{};
-	if (c0.slot >= 0)
-		r0 = ct_row_load(T, (uint32_t)c0.slot);
-	if (c1.slot >= 0)
-		r1 = ct_row_load(T, (uint32_t)c1.slot);
-	if (c2.slot >= 0)
-		r2 = ct_row_load(T, (uint32_t)c2.slot);
-	ctc_install<K>(T, c, k0, c0, r0, k0, k1, k2);
-	ctc_install<K>(T, c, k1, c1, r1, k0, k1, k2);
-	ctc_install<K>(T, c, k2, c2, r2, k0, k1, k2);
-}
-
 /* BPF_ANY update of k (ct_create's map_update_elem) through the cache */
 template <class K>
 __device__ __forceinline__ bool ctc_update(const ct_table &T, const ct_acct &A, ct_cache<K> &c,
@@ -7042,15 +6599,6 @@ __device__ __forceinline__ uint32_t ct_step(const ct_table &T, const ct_acct &A,
 {
 	const uint32_t meta = q.meta;
 	const bool ingress = !(meta & CTM_EGRESS);
-	{
-		/* reply key not cached, or cached absent: fetch it, the forward key
-		 * and (when the packet may create) the ICMP key in one round */
-		const int c1 = ctc_find<K>(c, k);
-		if (c1 < 0 || (ctc_state(c, c1) & CTC_NEG)) {
-			const typename K::key fk = K::reversed(k);
-			ctc_prefetch<K>(T, c, k, fk, K::related(fk), c1 < 0, true, (meta & CTM_ALLOWED) != 0);
-		}
-	}
 	int ci = ctc_get<K>(T, c, k);
 	uint32_t ret;
 	if (!(ctc_state(c, ci) & CTC_NEG)) {
@@ -7081,7 +6629,7 @@ __device__ __forceinline__ uint32_t ct_step(const ct_table &T, const ct_acct &A,
 	 * then the ICMP entry relating errors */
 	const ct_row e = ct_new_row<K>(q, ingress, now);
 	uint32_t owed = 0;
-	if (K::ADDR && CGPU_CT_CREATE_LOOP) {
+	if constexpr (K::ADDR) {
 	/* the service step's creates in order, t = 0 the forward entry, 1 the
 	 * address entry, 2 the ICMP entry, through ONE map-update call site:
 	 * three inlined copies took the CtK4S walker to 256 VGPRs with spills,
@@ -7092,24 +6640,20 @@ __device__ __forceinline__ uint32_t ct_step(const ct_table &T, const ct_acct &A,
 		typename K::key kt = k;
 		ct_row et = e;
 		if (t == 1) {
-			if constexpr (!K::ADDR) {
-				continue;
+			const uint32_t am = q.lbf >> 1;
+			if (am == AM_INLINE) {
+				kt = ct_addr_key(k, q);
 			} else {
-				const uint32_t am = q.lbf >> 1;
-				if (am == AM_INLINE) {
-					kt = ct_addr_key(k, q);
-				} else {
-					/* AM_DEFER: the entry lies in another address pair's
-					 * group: reserve its capacity now (the reference's
-					 * update fails here when the map is full), write it
-					 * in phase 2 */
-					if (am == AM_DEFER) {
-						if (!ct_take_k<K>(T, A, K::hash(k)))
-							return CT_NEW | CT_FAIL;
-						owed = CT_ADDRP;
-					}
-					continue;
+				/* AM_DEFER: the entry lies in another address pair's
+				 * group: reserve its capacity now (the reference's
+				 * update fails here when the map is full), write it
+				 * in phase 2 */
+				if (am == AM_DEFER) {
+					if (!ct_take_k<K>(T, A, K::hash(k)))
+						return CT_NEW | CT_FAIL;
+					owed = CT_ADDRP;
 				}
+				continue;
 			}
 		} else if (t == 2) {
 			et.c.y |= CTB_SEEN_NON_SYN;
@@ -7130,17 +6674,6 @@ __device__ __forceinline__ uint32_t ct_step(const ct_table &T, const ct_acct &A,
 	}
 	if (!ctc_update<K>(T, A, c, k, e))
 		return CT_NEW | CT_FAIL;
-	if constexpr (K::ADDR) {
-		const uint32_t am = q.lbf >> 1;
-		if (am == AM_INLINE) {
-			if (!ctc_update<K>(T, A, c, ct_addr_key(k, q), e))
-				return CT_NEW | CT_FAIL;
-		} else if (am == AM_DEFER) {
-			if (!ct_take_k<K>(T, A, K::hash(k)))
-				return CT_NEW | CT_FAIL;
-			owed = CT_ADDRP;
-		}
-	}
 	ct_row e2 = e;
 	e2.c.y |= CTB_SEEN_NON_SYN;
 	if (meta & CTM_RELX) {
@@ -7288,8 +6821,6 @@ __device__ __forceinline__ uint4 ct_svc_step(const cgpu_snapshot &s, const ct_ta
 	uint4 f = uint4{r.r0.x, kd | (r.r1.w & 0xFFFF0000u), r.r2.x, r.r2.y};
 	const uint4 drop = make_uint4(SVC_DROP, 0, 0, 0);
 	uint32_t slave, lbs = 0;
-	if (ctc_find<CtK4>(c, k) < 0) /* the service key and its ICMP key in one round */
-		ctc_prefetch<CtK4>(T, c, k, CtK4::related(k), k, true, true, false);
 	int ci = ctc_get<CtK4>(T, c, k);
 	if (!(ctc_state(c, ci) & CTC_NEG)) { /* CT_REPLY / CT_RELATED: the stored state */
 		ct_row e = ctc_row(c, ci);
@@ -7435,8 +6966,6 @@ __device__ __forceinline__ uint4 ct_svc_step6(const cgpu_snapshot &s, const ct_t
 	const uint32_t pr = r.r2.y & 0xFFu;
 	const uint4 drop = make_uint4(SVC_DROP, 0, 0, 0);
 	uint32_t slave, lbs = 0;
-	if (ctc_find<CtK6>(c, k) < 0)
-		ctc_prefetch<CtK6>(T, c, k, CtK6::related(k), k, true, true, false);
 	int ci = ctc_get<CtK6>(T, c, k);
 	if (!(ctc_state(c, ci) & CTC_NEG)) {
 		ct_row e = ctc_row(c, ci);
@@ -7878,7 +7407,7 @@ __global__ __launch_bounds__(256, K::ADDR ? CGPU_WALK_MINB_SVC : CGPU_WALK_W) vo
 	for (uint32_t h = blockIdx.x * 256u + threadIdx.x; h < nh; h += stride) {
 		const uint64_t p0 = a.gpos[h];
 		const uint64_t p1 = p0 + a.glen[h];
-		/* CGPU_CT_DFLT: the group's orientation (-1: not yet decided) */
+		/* CT_DFLT: the group's orientation (-1: not yet decided) */
 		int gb = -1;
 		/* packets in batch order through the sort permutation, software-
 		 * pipelined: the record of p + 1 and the index of p + 2 are in
@@ -8412,15 +7941,11 @@ static ct_args ct_args_of(const ct_launch &L)
 	return a;
 }
 
-/* 1: groups ordered longest first by power-of-two length buckets on the
- * device (no host read of the group count, no sort of the lengths); 0: the
+/* !exact: groups ordered longest first by power-of-two length buckets on the
+ * device (no host read of the group count, no sort of the lengths); exact: the
  * lengths radix-sorted exactly, after a host read.  The IPv6 walks keep the
  * exact order: ct 12.29 -> 12.16 ms and ctlb 22.40 -> 22.04 with the
  * buckets, ct6 15.70 -> 15.88 (profiles/r4_ad/) */
-#ifndef CGPU_CT_LH
-#define CGPU_CT_LH 1
-#endif
-
 /* Groups longest first, ordered on the device (the group count stays in
  * device memory: no host round trip between the sort and the walk).  A
  * group's bucket is the highest set bit of its length; the buckets are laid
@@ -8551,7 +8076,7 @@ static hipError_t ct_group_sort(const cgpu_snapshot &s, const ct_launch &L, ct_a
 	if (e != hipSuccess)
 		return e;
 	*nh = 0;
-	if (CGPU_CT_LH && !exact) {
+	if (!exact) {
 		/* gkey / idx are free again: (length, start) of the groups,
 		 * longest first; temp holds the range counts */
 		uint32_t *bh = static_cast<uint32_t *>(L.temp);
@@ -8794,7 +8319,7 @@ static hipError_t launch_ct(const cgpu_snapshot &s, const ct_table &T, const ct_
 	 * until the group sort) when it can fold the egress fallback identity */
 	const bool pre6 = s.cluster_id && s.cluster_id <= DIR_PAYLOAD_MASK;
 	/* the orientation-default results (CT_DFLT) with the Q preps */
-	if (!CGPU_CT_DFLT || (K::V6 && !pre6))
+	if (K::V6 && !pre6)
 		a.dflt = 0u;
 	const unsigned g = (unsigned)std::min<uint64_t>((L.n + 255) / 256, 8192);
 	/* cgpu_classify_v{4,6}_ct_tun: the preps write the forward tuple's tunnel
@@ -8908,7 +8433,7 @@ hipError_t launch_classify_v6_ctlb(const cgpu_snapshot &s, const ct_table &T, co
 	e = ct_svc_walk<CtK6>(s, T, L, a, st);
 	if (e != hipSuccess)
 		return e;
-	if (CGPU_CT_SVC_PRE6 && s.cluster_id && s.cluster_id <= DIR_PAYLOAD_MASK && !CGPU_CT_SVC_DECQ6) {
+	if (s.cluster_id && s.cluster_id <= DIR_PAYLOAD_MASK) {
 		/* as the plain IPv6 path: the ipcache lookups (on the translated
 		 * daddr) through the trie pre-pass into idx_sorted (free between
 		 * the service walk and the group sort), then Q packets per lane */
@@ -8924,7 +8449,6 @@ hipError_t launch_classify_v6_ctlb(const cgpu_snapshot &s, const ct_table &T, co
 	} else {
 		a.dflt = 0u; /* k_ct_prep6 stores every result */
 		hipLaunchKernelGGL(k_ct_prep6<true>, dim3(g), dim3(256), 0, st, s, a, tun_args{});
-		launch_ct_decq<CtK6S>(s, a, st);
 	}
 	if (T.lru) /* the actual records on top of the superset */
 		launch_ct_mark<CtK6S>(T, a, st);
@@ -8975,12 +8499,10 @@ hipError_t launch_classify_v4_ctlb(const cgpu_snapshot &s, const ct_table &T, co
 	e = hipMemsetAsync(a.ctl, 0, 16, st);
 	if (e != hipSuccess)
 		return e;
-	if (CGPU_CT_SVC_Q > 1) {
-		constexpr int Q = CGPU_CT_SVC_Q > 1 ? CGPU_CT_SVC_Q : 2;
+	{
+		constexpr int Q = CGPU_CT_SVC_Q;
 		const unsigned gq = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((L.n + 256 * Q - 1) / (256 * Q), 8192));
 		hipLaunchKernelGGL((k_ct_prep_svc_q<Q>), dim3(gq), dim3(256), 0, st, s, a, true);
-	} else {
-		hipLaunchKernelGGL((k_ct_prep<true, false>), dim3(g), dim3(256), 0, st, s, a, true);
 	}
 	uint32_t ctl[4];
 	e = hipMemcpyAsync(ctl, a.ctl, 16, hipMemcpyDeviceToHost, st);
@@ -8991,7 +8513,6 @@ hipError_t launch_classify_v4_ctlb(const cgpu_snapshot &s, const ct_table &T, co
 		a.dflt = 0u; /* one group: every result stored */
 		hipLaunchKernelGGL((k_ct_prep<true, true>), dim3(g), dim3(256), 0, st, s, a);
 	}
-	launch_ct_decq<CtK4S>(s, a, st);
 	if (T.lru) /* the actual records (after the serial re-prep) on top of the superset */
 		launch_ct_mark<CtK4S>(T, a, st);
 	e = ct_group_sort(s, L, a, L.n, &nh, st);
@@ -9017,7 +8538,7 @@ hipError_t launch_classify_v4_ctlb(const cgpu_snapshot &s, const ct_table &T, co
 			 * key (the filter in temp, free between the selection and the
 			 * sort) */
 			uint32_t *bl = nullptr;
-			if (ph == 1u && CGPU_OWED_BY_KEY) {
+			if (ph == 1u) {
 				bl = static_cast<uint32_t *>(L.temp);
 				if ((e = hipMemsetAsync(bl, 0, OWED_BLOOM_WORDS * 4u, st)) != hipSuccess)
 					return e;

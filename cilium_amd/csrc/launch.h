@@ -203,7 +203,7 @@ struct ct_launch {
 	uint64_t *pk;         /* [n_ctr_slots] packed counters, zero between calls */
 	void *xdaddr;         /* [n] optional (IPv6: 16 bytes each) */
 	uint16_t *xdport;     /* [n] optional */
-	uint32_t dflt;        /* nonzero: group-default results (CGPU_CT_DFLT) */
+	uint32_t dflt;        /* nonzero: group-default results (CT_DFLT) */
 	/* cgpu_classify_v{4,6}_ct_tun: [n] tunnel endpoints out (NULL: none) from
 	 * the tunnel tables `tun` (plain paths only) */
 	uint32_t *tunnel;

@@ -30,26 +30,29 @@ VARIANTS = {"product": (), "no_cold_atomics": ("CGPU_DIAG_NO_COLD",),
             "store_sc1": ("CGPU_DIAG_STORE_SC1",),
             "pf6_no_node": ("CGPU_DIAG_PF6_NO_NODE",), "pf6_no_ep": ("CGPU_DIAG_PF6_NO_EP",),
             "pf6_no_cover": ("CGPU_DIAG_PF6_NO_COVER",),
-            "pf6_prefetch": ("CGPU_DIAG_PF6_PREFETCH",),
             "pf6_q4": ("CGPU_DIAG_PF6_Q=4",),
             "pf6_q2": ("CGPU_DIAG_PF6_Q=2",),
-            "pf6_q2_prefetch": ("CGPU_DIAG_PF6_Q=2", "CGPU_DIAG_PF6_PREFETCH"),
+            # (pf6_prefetch, the next step's addresses loaded early: 2.55 against 1.97 ms with spills, then 1.124 against 1.137: r2_pf6b/diag_ab_history.log c, f)
+            # (pf6_q2_prefetch, the same at two packets per lane: 1.115 against 1.141 ms, no gain over the product's 1.137: r2_pf6b/diag_ab_history.log f)
             "ct_coherent_probe": ("CGPU_DIAG_CT_COHERENT_PROBE",),
             "walk_clock": ("CGPU_DIAG_WALK_CLOCK",),
             "v6_q3": ("CGPU_DIAG_V6_Q=3",), "v6_q4": ("CGPU_DIAG_V6_Q=4",),
             "v6_no_trie": ("CGPU_DIAG_V6_NO_TRIE",), "v6_l64": ("CGPU_V6T_NB=7",),
             "v6_l64_q3": ("CGPU_V6T_NB=7", "CGPU_DIAG_V6_Q=3"),
             "v6_pre_q1": ("CGPU_DIAG_IPC6_PRE_Q=1",), "v6_pre_q4": ("CGPU_DIAG_IPC6_PRE_Q=4",),
-            "ct_prefetch": ("CGPU_CT_PREFETCH",),
+            # (ct_prefetch, a step's three conntrack keys probed together: ct 21.94 against 18.54 ms: r3_ct_ab/ab_ct.log)
             "ctc3": ("CTC=3",), "ctc2": ("CTC=2",),
             "v6_no_h64": ("CGPU_DIAG_V6_NO_H64",), "v6_pre_w2": ("CGPU_IPC6_MINW=2",), "v6_pre_q1_w2": ("CGPU_IPC6_MINW=2", "CGPU_DIAG_IPC6_PRE_Q=1"),
             "v6_pre_q4_w2": ("CGPU_IPC6_MINW=2", "CGPU_DIAG_IPC6_PRE_Q=4"), "ct_q2": ("CGPU_CT_Q=2",), "ct_q1": ("CGPU_CT_Q=1",),
-            "policy_probes": ("CGPU_POLICY_Q_PROBES=1",), "walk_svc_minb1": ("CGPU_WALK_MINB_SVC=1",),
-            "svc_decq": ("CGPU_CT_SVC_DECQ=1",), "svc_decq6": ("CGPU_CT_SVC_DECQ6=1",),
+            "walk_svc_minb1": ("CGPU_WALK_MINB_SVC=1",),
+            # (policy_probes, probes 1 and 2 themselves instead of the group slot: ct 12.34 against 12.11 ms, ct6 15.54 against 15.39, ctlb 29.87 against 30.06: r4_i/ab_*.log)
+            # (svc_decq, the IPv4 service path's decisions in a pass of their own: ctlb 25.53 against 25.19 ms: r4_o/ab_ctlb.log)
+            # (svc_decq6, the same on IPv6: ctlb6 26.93 against 24.13 ms per 256-thread workgroup, 24.75 against 24.10 on a resident grid: r4_o/ab_ctlb6.log, r4_s/ab_ctlb6.log)
             "walk_w4": ("CGPU_WALK_W=4",), "walk_w3": ("CGPU_WALK_W=3",),
             "cc_probe2": ("CC_PROBE=2",), "cc_probe4": ("CC_PROBE=4",),
-            "owed_by_pair": ("CGPU_OWED_BY_KEY=0",), "ct_len_sort": ("CGPU_CT_LH=0",),
-            "v6_full_line": ("CGPU_V6T_FULL_LINE=1",),
+            # (owed_by_pair, phase 2b's address entries grouped by pair, not by key: ctlb 23.59 against 22.42 ms: r4_ac/ab_ctlb.log)
+            # (ct_len_sort, the IPv4 groups' lengths sorted exactly: ct 12.29 against 12.16 ms, ctlb 22.40 against 22.04; ct6 15.70 against 15.88, so IPv6 keeps the exact order: r4_ad/ab_*.log)
+            # (v6_full_line, a trie node's whole 128-B line in one read: v6 4.68 against 2.86 ms: r5_d/ab_v6.log)
             "hs_g256": ("CGPU_HS_COPY_G=256",), "hs_g512": ("CGPU_HS_COPY_G=512",),
             "hs_g64": ("CGPU_HS_COPY_G=64",), "hs_chunk23": ("CGPU_HS_CHUNK_LOG2=23",),
             "hs_chunk21": ("CGPU_HS_CHUNK_LOG2=21",), "hs_chunk24": ("CGPU_HS_CHUNK_LOG2=24",),
@@ -59,20 +62,23 @@ VARIANTS = {"product": (), "no_cold_atomics": ("CGPU_DIAG_NO_COLD",),
             "walk_grid8192": ("CT_WALK_GRID=8192",), "retb32": ("CT_RETB=32",),
             "g4096_retb32": ("CT_WALK_GRID=4096", "CT_RETB=32"), "g8192_retb32": ("CT_WALK_GRID=8192", "CT_RETB=32"),
             "walk_grid16384": ("CT_WALK_GRID=16384",), "walk_grid32768": ("CT_WALK_GRID=32768",),
-            "ff_nostage": ("CGPU_FF_STAGE=0",), "ff_pool0": ("CGPU_FF_POOL=0",), "ff_pool8": ("CGPU_FF_POOL=8",),
+            "ff_pool8": ("CGPU_FF_POOL=8",),
+            # (ff_nostage, fused frames with per-lane slot loads: 2.96 against 2.64 ms: r5_j/ab_frames_fused.log)
+            # (ff_pool0, a staging buffer per wave: frames 2.60 against 2.52 ms: r5_l/ab_frames_pool.log)
             "ff_pool2": ("CGPU_FF_POOL=2",), "fin_q2": ("CGPU_CT_FQ=2",), "fin_q3": ("CGPU_CT_FQ=3",), "fin_q4": ("CGPU_CT_FQ=4",),
             "prep_q3": ("CGPU_CT_Q=3",), "prep_q2": ("CGPU_CT_Q=2",),
             "fin_nt512": ("CGPU_CT_FNT=512",), "fin_q3_nt512": ("CGPU_CT_FQ=3", "CGPU_CT_FNT=512"),
             "fin_q2_nt512": ("CGPU_CT_FQ=2", "CGPU_CT_FNT=512"), "walk_svc_minb3": ("CGPU_WALK_MINB_SVC=3",),
-            "ct_create_noloop": ("CGPU_CT_CREATE_LOOP=0",),
-            "svc_q1": ("CGPU_CT_SVC_Q=1",), "svc_q2": ("CGPU_CT_SVC_Q=2",), "svc_q4": ("CGPU_CT_SVC_Q=4",),
-            "svc_pre6_off": ("CGPU_CT_SVC_PRE6=0",), "ff_h1": ("CGPU_FF_H=1",), "ff_h4": ("CGPU_FF_H=4",),
+            # (ct_create_noloop, the service step's three creates each with its own map update: 256 VGPRs with spills against 186, which fit three workgroups per CU, ctlb 20.83 against 20.64 ms: DESIGN.md "Round 5", r5_k/ab_ctlb_minb.log)
+            "svc_q2": ("CGPU_CT_SVC_Q=2",), "svc_q4": ("CGPU_CT_SVC_Q=4",),
+            # (svc_q1, the per-lane service prep: ctlb 20.61 against 20.40 ms: r5_k/ab_ctlb_svc_q.log)
+            # (svc_pre6_off, the IPv6 service prep without the trie pre-pass: ctlb6 22.46 against 22.16 ms: r5_k/ab_ctlb6_pre6.log)
+            "ff_h1": ("CGPU_FF_H=1",), "ff_h4": ("CGPU_FF_H=4",),
             # policy table slots per key (hopscotch, round 6): 2 = 2 MiB at config 2
             # (the product), 4 = 4 MiB, 8 = 8 MiB (round 5's footprint)
             "pol_spk4": ("CGPU_POL_SLOTS_PER_KEY=4",), "pol_spk8": ("CGPU_POL_SLOTS_PER_KEY=8",),
             "pol_spk2": ("CGPU_POL_SLOTS_PER_KEY=2",),
-            # the v6 pre-pass: addresses behind the direction flag (round 5's form)
-            "v6_pre_nospec": ("CGPU_IPC6_SPEC=0",),
+            # (v6_pre_nospec, the v6 pre-pass's addresses loaded behind the direction flag, round 5's form: 2.837 against 2.809 ms: r6_h/ab_v6_pre.log)
             "v6_pre_q3": ("CGPU_DIAG_IPC6_PRE_Q=3",), "v6_pre_q4b": ("CGPU_DIAG_IPC6_PRE_Q=4",),
             # LB frontend slots per frontend (hopscotch, round 6): 2 = 32 MiB at config 5
             "lb_fe4": ("CGPU_LB_SLOTS_PER_FE=4",), "lb_fe8": ("CGPU_LB_SLOTS_PER_FE=8",),
@@ -83,7 +89,9 @@ VARIANTS = {"product": (), "no_cold_atomics": ("CGPU_DIAG_NO_COLD",),
             # macro left the tree with the result)
             # the cascade kernel's tuples per lane (product 2, r6_l; sep_q2 was
             # the same define on the stages-apart source)
-            "xdp_q4": ("CGPU_XDP_Q=4",), "no_defer_cold": ("CGPU_X4_DEFER_COLD=0",), "no_ct_dflt": ("CGPU_CT_DFLT=0",),
+            "xdp_q4": ("CGPU_XDP_Q=4",),
+            # (no_defer_cold, the x4 kernel's cold-slot atomics ahead of the next quad's loads: config 2 1.61-1.62 against 1.59-1.60 ms, v6 2.69 against 2.66: r6_n/ab_defer_gpu.log, ab_defer_v6.log)
+            # (no_ct_dflt, every conntrack result stored: ct 11.00 against 10.45-10.57 ms, r7_c/ab.log; ct6 14.44 against 14.18, ctlb 19.8 against 19.3: r7_d)
             # (group-default conntrack results, the walker storing only the
             # results that differ from its group's orientation default and the
             # finish resolving the rest from a 2-MiB bitmap: ct 10.95 -> 10.73

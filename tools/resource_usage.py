@@ -14,6 +14,17 @@ LDS.  `diff` compares two tables by kernel name, matching a kernel whose
 template arguments a change appended to (all appended ones `false`) with the
 name it had before, and exits 1 when a kernel of the first table is missing
 from the second or differs in any column.
+
+    hipcc --offload-arch=gfx950 -O3 -std=c++17 -I include --cuda-device-only \\
+          -S cilium_amd/csrc/kernels.hip -o branch.s
+    python tools/resource_usage.py isa parent.s branch.s
+
+`isa` compares two assembly listings function by function (kernels and the
+device functions left out of line), ignoring comments, debug lines and the
+numbers in compiler-local labels, which renumber when an earlier function
+goes; it names the functions that differ or exist on one side only and exits
+1 when one differs.  (Assembly, not linked objects: those differ in
+pc-relative literals once anything moves.)
 """
 import re
 import subprocess
@@ -116,10 +127,46 @@ def diff(pa, pb):
     return 1 if bad else 0
 
 
+def functions(path):
+    """{symbol: its assembly from .type to .Lfunc_end and the .size / .set
+    lines behind it}, without comments, .loc / .file lines and the numbers of
+    compiler-local labels"""
+    out, cur, ending = {}, None, False
+    for line in open(path, errors="replace"):
+        line = line.split(";", 1)[0].rstrip()
+        m = re.match(r"\s*\.type\s+(\S+),@function", line)
+        if m:
+            cur, ending = out.setdefault(m.group(1), []), False
+        if cur is None or not line.strip() or re.match(r"\s*\.(loc|file)\s", line):
+            continue
+        if ending and not re.match(r"\s*\.(size|set)\s", line):
+            cur = None
+            continue
+        ending = ending or re.match(r"\.Lfunc_end\d+:", line) is not None
+        cur.append(re.sub(r"\.(LBB|Ltmp|LJTI|Lfunc_begin|Lfunc_end)\d+", r".\1", line))
+    return out
+
+
+def isa(pa, pb):
+    a, b = functions(pa), functions(pb)
+    dm = demangle(sorted(set(a) | set(b)))
+    differ = [n for n in a if n in b and a[n] != b[n]]
+    for n in sorted(differ, key=dm.get):
+        print(f"DIFFERS: {dm[n]}")
+    for path, x, y in ((pa, a, b), (pb, b, a)):
+        for n in sorted(set(x) - set(y), key=dm.get):
+            print(f"ONLY IN {path}: {dm[n]}")
+    print(f"{len(set(a) & set(b)) - len(differ)} functions identical, {len(differ)} differing; "
+          f"{len(set(a) - set(b))} only in {pa}, {len(set(b) - set(a))} only in {pb}")
+    return 1 if differ else 0
+
+
 if __name__ == "__main__":
     if len(sys.argv) == 3 and sys.argv[1] == "table":
         table(sys.argv[2])
     elif len(sys.argv) == 4 and sys.argv[1] == "diff":
         sys.exit(diff(sys.argv[2], sys.argv[3]))
+    elif len(sys.argv) == 4 and sys.argv[1] == "isa":
+        sys.exit(isa(sys.argv[2], sys.argv[3]))
     else:
         sys.exit(__doc__)
