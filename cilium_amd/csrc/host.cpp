@@ -2030,10 +2030,15 @@ struct cgpu_ctx {
 	 * classify calls; one per stream keeps its exactness bound per call).
 	 * At most kMaxPkStreams buffers: a new stream past that takes the least
 	 * recently used one once that stream's last launch finished (`last`). */
+	/* log: the x4 classify kernels' cold-hit log (launch.h pk_log), allocated
+	 * by the stream's first call that wants one and grown, once the stream's
+	 * last launch finished, by a call that wants a larger one. */
 	struct PkBuf {
 		uint64_t *p = nullptr;
 		hipEvent_t last = nullptr;
 		uint64_t tick = 0;
+		uint32_t *log = nullptr;
+		size_t log_bytes = 0;
 	};
 	std::map<void *, PkBuf> d_pk;
 	uint64_t pk_tick = 0;
@@ -2339,6 +2344,7 @@ CGPU_EXPORT void cgpu_ctx_destroy(cgpu_ctx *c)
 			std::lock_guard<std::mutex> g(c->pk_mu);
 			for (auto &kv : c->d_pk) {
 				(void)hipFree(kv.second.p);
+				(void)hipFree(kv.second.log);
 				if (kv.second.last)
 					(void)hipEventDestroy(kv.second.last);
 			}
@@ -4994,6 +5000,10 @@ static int pin(cgpu_ctx *c, void *stream, Pinned &p, bool want_pk = false)
 				HIP_OR_EIO(hipEventSynchronize(lru->second.last));
 				b = lru->second;
 				c->d_pk.erase(lru);
+				/* (its log goes: sized for that stream's calls) */
+				(void)hipFree(b.log);
+				b.log = nullptr;
+				b.log_bytes = 0;
 			} else {
 				const size_t bytes = (size_t)c->n_ctr_slots * 8;
 				HIP_OR_EIO(hipMalloc((void **)&b.p, bytes));
@@ -5011,6 +5021,45 @@ static int pin(cgpu_ctx *c, void *stream, Pinned &p, bool want_pk = false)
 	return 0;
 }
 
+/* The pinned stream's cold-hit log, at least `want` bytes (x4_log_bytes of
+ * the call about to be launched; 0: the call does not log, nothing is
+ * allocated).  Growing it waits for the stream's last launch, which may still
+ * read the old one; the wait runs without pk_mu, so other streams' calls go
+ * on (the calls on one stream come from one thread at a time, cgpu.h).  A
+ * failed allocation leaves the call without a log: the launch then takes the
+ * atomic for every cold hit. */
+static pk_log pin_log(Pinned &p, size_t want)
+{
+	if (!want || !p.pk)
+		return pk_log{nullptr, 0};
+	cgpu_ctx *c = p.c;
+	hipEvent_t last = nullptr;
+	{
+		std::lock_guard<std::mutex> g(c->pk_mu);
+		auto it = c->d_pk.find((void *)p.st);
+		if (it == c->d_pk.end() || it->second.p != p.pk)
+			return pk_log{nullptr, 0};
+		if (want <= it->second.log_bytes)
+			return pk_log{it->second.log, it->second.log_bytes / 4u};
+		last = it->second.last;
+	}
+	if (hipEventSynchronize(last) != hipSuccess)
+		return pk_log{nullptr, 0};
+	std::lock_guard<std::mutex> g(c->pk_mu);
+	auto it = c->d_pk.find((void *)p.st);
+	if (it == c->d_pk.end() || it->second.p != p.pk)
+		return pk_log{nullptr, 0};
+	cgpu_ctx::PkBuf &b = it->second;
+	(void)hipFree(b.log);
+	b.log = nullptr;
+	b.log_bytes = 0;
+	if (hipMalloc((void **)&b.log, want) == hipSuccess)
+		b.log_bytes = want;
+	else
+		(void)hipGetLastError();
+	return pk_log{b.log, b.log_bytes / 4u};
+}
+
 CGPU_EXPORT int cgpu_stream_release(cgpu_ctx *c, void *stream)
 {
 	if (!c)
@@ -5024,6 +5073,7 @@ CGPU_EXPORT int cgpu_stream_release(cgpu_ctx *c, void *stream)
 	HIP_OR_EIO(hipSetDevice(c->device));
 	HIP_OR_EIO(hipEventSynchronize(it->second.last));
 	(void)hipFree(it->second.p);
+	(void)hipFree(it->second.log);
 	(void)hipEventDestroy(it->second.last);
 	c->d_pk.erase(it);
 	return 0;
@@ -5073,6 +5123,7 @@ static int classify_v4_path(cgpu_ctx *c, const cgpu_tuples_v4 *t, const uint16_t
 	a.tunnel = tunnel;
 	a.tun = &P.tun();
 	HIP_OR_EIO(hipSetDevice(c->device));
+	a.log = pin_log(P, x4_log_bytes(s, a));
 	HIP_OR_EIO(launch_classify_v4(s, a, (hipStream_t)stream));
 	return 0;
 }
@@ -5530,6 +5581,7 @@ static int v4_host(cgpu_ctx *c, const cgpu_tuples_v4 *t, const uint16_t *sport, 
 			else
 				a.sport = reinterpret_cast<const uint16_t *>(di[7]);
 		}
+		a.log = pin_log(P, x4_log_bytes(s, a));
 		HIP_OR_EIO(launch_classify_v4(s, a, cs));
 		return 0;
 	});

@@ -1142,6 +1142,13 @@ struct cls_args {
 	/* k_classify_x4 IPCE: the ipcache entries k_ipc6_pre wrote, [n] */
 	uint32_t *ipc_e;
 	int xdp; /* v4 with lb: the XDP prefilter before every ingress tuple (cgpu_classify_v4_cascade) */
+	/* k_classify_x4's cold-hit log (cold_log_append): the stream's buffer as
+	 * the caller hands it in (lg), and what launch_x4 carves from it for a
+	 * launch: wave w's entries at log + w * log_region, its count in log_n[w];
+	 * log_region 0: no log, every cold hit is an atomic on pk */
+	pk_log lg;
+	uint32_t *log, *log_n;
+	uint32_t log_region;
 };
 
 /* The identity resolution and the three-probe policy cascade for one tuple
@@ -1644,6 +1651,124 @@ __global__ __launch_bounds__(NT) void k_classify(cgpu_snapshot s, cls_args a, tu
 #define PKC_MAX_LEN (1u << 11)
 #define PKC_CHUNK (1ull << 26)
 
+/* Cold-hit log.  A counter hit of < PKC_MAX_LEN bytes on a cold slot (one
+ * past the LDS hot slots) that no LDS counter took used to be one 8-byte
+ * global atomic on pk: a memory-side request to a random line, which also
+ * holds the wave's later loads back while it is outstanding (vmcnt retires in
+ * order).  Instead the wave appends one word per hit, cold_log_entry, to a
+ * region of the stream's log that it alone writes, with plain consecutive
+ * stores; k_cold_hist sums the launch's log into pk before k_unpack.  An
+ * entry that finds its region full takes the atomic, so any region size is
+ * exact.  The helpers are kept apart from k_classify_x4 so that k_ct_finish,
+ * whose cold path is the same, can take them. */
+#define COLD_LOG_NONE 0xFFFFFFFFu
+#define COLD_LOG_LEN_BITS 11u
+#define COLD_LOG_SLOT_BITS (32u - COLD_LOG_LEN_BITS)
+static_assert((1u << COLD_LOG_LEN_BITS) == PKC_MAX_LEN, "a logged hit's bytes fit the entry");
+
+/* cold: the slot less hot_slots, < 2^COLD_LOG_SLOT_BITS; len < PKC_MAX_LEN */
+__device__ __forceinline__ uint32_t cold_log_entry(uint32_t cold, uint32_t len)
+{
+	return (cold << COLD_LOG_LEN_BITS) | len;
+}
+
+/* One append round, called by the live lanes of a wave together: the lanes
+ * whose e is an entry store it at consecutive words from the wave's cursor
+ * (one or two write requests), the cursor moves past them.  cur counts every
+ * entry, those past the region too (they went to pk[hot + slot]). */
+__device__ __forceinline__ void cold_log_append(uint32_t *reg, uint32_t region, uint32_t &cur, uint32_t e,
+						uint64_t *pk, uint32_t hot)
+{
+	const bool has = e != COLD_LOG_NONE;
+	const uint64_t m = __ballot(has);
+	if (has) {
+		const uint32_t pos =
+			cur + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+		if (pos < region)
+			reg[pos] = e;
+		else
+			atomicAdd((unsigned long long *)&pk[hot + (e >> COLD_LOG_LEN_BITS)],
+				  (1ull << PKC_SHIFT) | (unsigned long long)(e & (PKC_MAX_LEN - 1u)));
+	}
+	cur += (uint32_t)__popcll(m);
+}
+
+/* The wave's entry count for k_cold_hist, written by one lane at the end of
+ * the kernel (every lane of the wave calls; a lane that left the tuple loop
+ * early holds a smaller cursor). */
+__device__ __forceinline__ void cold_log_close(uint32_t *count, uint32_t region, uint32_t cur)
+{
+#pragma unroll
+	for (int off = 32; off > 0; off >>= 1)
+		cur = max(cur, (uint32_t)__shfl_xor((int)cur, off, 64));
+	if ((threadIdx.x & 63u) == 0u)
+		*count = min(cur, region);
+}
+
+/* The second pass over a launch's log: workgroup (p, r) = blockIdx.x / R, % R
+ * sums the entries of cold slots [p * per, (p + 1) * per) in the regions of
+ * waves r, r + R, .. < waves into LDS, then adds every touched slot into pk,
+ * consecutive lanes on consecutive slots as k_classify_x4's hot flush does.
+ * `waves` is what the classify launch started: the counts of a larger
+ * earlier launch's other waves are stale.  LDS holds PKC words (not PK: a
+ * workgroup may meet any share of the launch's <= PKC_CHUNK hits on a slot). */
+template <int NT>
+__global__ __launch_bounds__(NT) void k_cold_hist(uint64_t *pk, const uint32_t *log, const uint32_t *log_n,
+						  uint32_t waves, uint32_t region, uint32_t hot, uint32_t n_cold,
+						  uint32_t per, uint32_t R)
+{
+	extern __shared__ __attribute__((aligned(16))) uint64_t hist[];
+	const uint32_t p = blockIdx.x / R, r = blockIdx.x % R;
+	const uint32_t lo = p * per;
+	const uint32_t cnt = min(per, n_cold - lo);
+	for (uint32_t k = threadIdx.x; k < cnt; k += NT)
+		hist[k] = 0;
+	__syncthreads();
+	/* A region per wave at a time, four entries per lane and load, HIST_U
+	 * loads of a lane in flight together (the pass is latency-bound: the
+	 * one-load-at-a-time form measured 43 us at config 2).  A load past the
+	 * count reads the region's first words instead of branching (region is a
+	 * multiple of 4 words, so every load stays inside it) and k < n drops
+	 * them; the next region's count is loaded beside this region's entries. */
+	constexpr uint32_t HIST_U = 8u;
+	const uint32_t lane = threadIdx.x & 63u;
+	const uint32_t stride = R * (NT / 64);
+	uint32_t w = r + R * (threadIdx.x >> 6);
+	uint32_t n_w = w < waves ? log_n[w] : 0u;
+	for (; w < waves; w += stride) {
+		const uint32_t n = min(n_w, region);
+		n_w = log_n[w + stride < waves ? w + stride : w];
+		const uint32_t *reg = log + (size_t)w * region;
+		for (uint32_t k0 = lane * 4u; k0 - lane * 4u < n; k0 += 256u * HIST_U) {
+			uint4 q[HIST_U];
+#pragma unroll
+			for (uint32_t j = 0; j < HIST_U; j++) {
+				const uint32_t k = k0 + 256u * j;
+				q[j] = *reinterpret_cast<const uint4 *>(reg + (k < n ? k : 0u));
+			}
+#pragma unroll
+			for (uint32_t j = 0; j < HIST_U; j++) {
+				const uint32_t k = k0 + 256u * j;
+				const uint32_t e4[4] = {q[j].x, q[j].y, q[j].z, q[j].w};
+#pragma unroll
+				for (uint32_t i = 0; i < 4u; i++) {
+					const uint32_t c = (e4[i] >> COLD_LOG_LEN_BITS) - lo;
+					if (k + i < n && c < cnt)
+						atomicAdd((unsigned long long *)&hist[c],
+							  (1ull << PKC_SHIFT) |
+								  (unsigned long long)(e4[i] & (PKC_MAX_LEN - 1u)));
+				}
+			}
+		}
+	}
+	__syncthreads();
+	for (uint32_t k = threadIdx.x; k < cnt; k += NT) {
+		const uint64_t x = hist[k];
+		if (x)
+			atomicAdd((unsigned long long *)&pk[hot + lo + k], (unsigned long long)x);
+	}
+}
+
 /* timing-only tool builds (tools/diag_ab.py; wrong results): confine a
  * gather to the first 1024 entries of its table, i.e. make it an L2 hit */
 #ifdef CGPU_DIAG_P1_SMALL
@@ -1870,7 +1995,9 @@ struct ftuple {
 #define FR_LXC_LDS 256u
 /* the x4 schedule's cold-slot atomics of a full quad go out behind the next
  * quad's column loads: config 2 1.612 -> 1.592 ms, v6 2.688 -> 2.661
- * (deferring the output stores as well: 2.08 ms, spills; profiles/r6_n/) */
+ * (deferring the output stores as well: 2.08 ms, spills; profiles/r6_n/).
+ * The plain kernel logs its cold hits instead (cold_log_append) and defers
+ * its atomics only in a launch that has no log. */
 #ifndef CGPU_FF_H
 #define CGPU_FF_H 2 /* fused frames: slots loaded together (1, 2, 4) */
 #endif
@@ -1990,10 +2117,24 @@ __global__ __launch_bounds__(NT, MINW) void k_classify_x4(cgpu_snapshot s, cls_a
 	__syncthreads();
 
 	const uint32_t lane = threadIdx.x & 63u;
-	/* DEFER: a quad's cold-slot atomics (into pk) are issued
-	 * after the next quad's column loads, so the wait for those loads does
-	 * not wait for them too (vmcnt retires in issue order) */
+	/* LOG: the plain kernel appends its cold hits to the cold-hit log
+	 * (cold_log_append) when the launch has one (a.log_region != 0).  The
+	 * other instantiations keep the atomics: with the log, config 5's kernel
+	 * gained 0.024 ms per 64M tuples and the fused frames kernel 0.052, and
+	 * k_cold_hist took 0.047 and 0.057 + 0.005 (profiles/cold_log/). */
+	constexpr bool LOG = QX;
+	/* the wave's region of the log and its cursor (the wave keeps its id
+	 * across the grid-stride loop) */
+	const uint32_t log_region = LOG ? a.log_region : 0u;
+	uint32_t *const log_w = a.log + (size_t)(t0 >> 6) * log_region;
+	uint32_t log_cur = 0u;
+	/* DEFER: a quad's cold-slot atomics (into pk) are issued after the next
+	 * quad's column loads, so the wait for those loads does not wait for
+	 * them too (vmcnt retires in issue order).  The plain kernel defers them
+	 * only in a launch without a log; with one, dcs stays empty (an entry
+	 * the log turns away takes its atomic at once). */
 	constexpr bool DEFER = !FF && Q == 4;
+	static_assert(!LOG || DEFER, "the logging kernel's launches without a log defer their atomics");
 	uint32_t dcs[DEFER ? Q : 1], dln[DEFER ? Q : 1];
 #pragma unroll
 	for (int u = 0; u < (DEFER ? Q : 1); u++)
@@ -2713,8 +2854,14 @@ __global__ __launch_bounds__(NT, MINW) void k_classify_x4(cgpu_snapshot s, cls_a
 		/* counters, outputs, metrics */
 		int32_t v[QA];
 		uint64_t *metg = a.delta + 2ull * s.n_ctr_slots;
+		/* LOG: the tuples' cold hits that no LDS counter took, logged (or
+		 * added to pk) behind this loop, where the wave's live lanes are
+		 * together */
+		uint32_t cs[LOG ? Q : 1];
 #pragma unroll
 		for (int u = 0; u < Q; u++) {
+			if constexpr (LOG)
+				cs[u] = COLD_LOG_NONE;
 			if (FR && (fw[u] & F_DEC)) {
 				/* k_frames' rules: NOT_CLASSIFIED counts nothing (stage 7), an
 				 * IPv6 frame's placeholder is overwritten by the v6 pass */
@@ -2787,7 +2934,9 @@ __global__ __launch_bounds__(NT, MINW) void k_classify_x4(cgpu_snapshot s, cls_a
 						}
 					}
 					if (!done) {
-						if constexpr (DEFER) {
+						if constexpr (LOG) {
+							cs[u] = c;
+						} else if constexpr (DEFER) {
 							dcs[u] = c;
 							dln[u] = len[u];
 						} else {
@@ -2812,6 +2961,24 @@ __global__ __launch_bounds__(NT, MINW) void k_classify_x4(cgpu_snapshot s, cls_a
 				const uint32_t mi = (mr * 2u + ((fw[u] & F_EG) ? 1u : 0u)) * 2u;
 				atomicAdd(&lmet[mi], 1ull);
 				atomicAdd(&lmet[mi + 1u], (unsigned long long)len[u]);
+			}
+		}
+		if constexpr (LOG) {
+			if (log_region) {
+#pragma unroll
+				for (int u = 0; u < Q; u++)
+					cold_log_append(log_w, log_region, log_cur,
+							cs[u] == COLD_LOG_NONE ? COLD_LOG_NONE
+									       : cold_log_entry(cs[u] - s.hot_slots, len[u]),
+							pk, s.hot_slots);
+			} else {
+				/* no log for this launch: the parent's path, the quad's
+				 * atomics deferred (COLD_LOG_NONE is dcs's empty mark) */
+#pragma unroll
+				for (int u = 0; u < Q; u++) {
+					dcs[u] = cs[u];
+					dln[u] = len[u];
+				}
 			}
 		}
 		if constexpr (FF) {
@@ -2868,6 +3035,10 @@ __global__ __launch_bounds__(NT, MINW) void k_classify_x4(cgpu_snapshot s, cls_a
 		}
 	}
 
+	if constexpr (LOG) {
+		if (log_region)
+			cold_log_close(a.log_n + (t0 >> 6), log_region, log_cur);
+	}
 	uint64_t *met = a.delta + 2ull * s.n_ctr_slots;
 #pragma unroll
 	for (int e = 0; e < 2; e++) {
@@ -3916,7 +4087,8 @@ static unsigned resident_blocks(const void *kern, int NT, size_t lds)
 
 /* x4 schedule: one persistent-size grid (every workgroup resident, so the
  * per-workgroup LDS counter flush is paid once per resident workgroup) per
- * launch of <= PKC_CHUNK tuples, then the unpack of pk into delta. */
+ * launch of <= PKC_CHUNK tuples, then the cold-hit log's second pass
+ * (k_cold_hist) and the unpack of pk into delta. */
 /* dynamic LDS of a k_classify_x4 workgroup: 160 KiB per CU less the static
  * metrics block and some slack */
 #define X4_LDS_BUDGET (156u * 1024u)
@@ -3931,6 +4103,55 @@ static uint32_t cc_entries(size_t used)
 		return 0u;
 	const size_t n = std::min<size_t>((X4_LDS_BUDGET - used) / 12u, 16384u) & ~(size_t)63u;
 	return n >= 512u ? (uint32_t)n : 0u;
+}
+
+/* k_cold_hist reads the log once per partition of the cold slots: past this
+ * many the log costs more than the atomics it replaces (cgpu.h
+ * CGPU_SCHED_NO_COLD_LOG) */
+#define COLD_HIST_MAX_P 8u
+
+/* k_cold_hist's partitions of the cold slots of `s` (a launch's snapshot,
+ * with_lds_hot applied): P of them, `per` slots each, within the LDS budget
+ * as PKC words.  False: the launch keeps the atomics (CGPU_SCHED_NO_COLD_LOG,
+ * no cold slot, more than COLD_HIST_MAX_P partitions, a cold slot index that
+ * does not fit an entry). */
+static bool cold_hist_parts(const cgpu_snapshot &s, uint32_t &n_cold, uint32_t &P, uint32_t &per)
+{
+	n_cold = s.cold_hi > s.hot_slots ? s.cold_hi - s.hot_slots : 0u;
+	P = (n_cold + X4_LDS_BUDGET / 8u - 1u) / (X4_LDS_BUDGET / 8u);
+	per = P ? (n_cold + P - 1u) / P : 0u;
+	return !(s.schedule & CGPU_SCHED_NO_COLD_LOG) && n_cold && P <= COLD_HIST_MAX_P &&
+	       n_cold <= (1u << COLD_LOG_SLOT_BITS);
+}
+
+/* LDS a plain IPv4 x4 launch takes besides the hot counters: the leaf
+ * dictionary, rounded to the counters' 8 bytes */
+static size_t x4_fixed_lds_v4(const cgpu_snapshot &s)
+{
+	return ((size_t)s.ipc4c.n_dict * 4u + 7u) & ~(size_t)7u;
+}
+
+static cgpu_snapshot with_lds_hot(const cgpu_snapshot &s, size_t max_hot);
+
+/* 0 unless launch_classify_v4 will log this call's cold hits: the x4
+ * schedule's plain kernel (no service step, no tunnel output, aligned
+ * columns) and partitions k_cold_hist takes.  Then 4 bytes for every fourth
+ * tuple of a launch (config 2 logs one tuple in ten): a launch of m tuples
+ * rounds m up to whole trips of its grid, less than one more trip of at most
+ * ceil(m / 4096) and at most 512 workgroups of 4096 tuples; and the waves'
+ * counts (launch_x4). */
+size_t x4_log_bytes(const cgpu_snapshot &s0, const classify_v4_args &x)
+{
+	const cls_args c{x.saddr, x.daddr, x.dport, x.proto, x.flags, x.len, x.ep, x.verdict, x.identity,
+			 x.stage, x.delta, x.n, x.pk, x.lb, x.sport, x.hash};
+	if ((s0.schedule & (CGPU_SCHED_PER_LANE | CGPU_SCHED_GLOBAL_CTR)) || !x.pk || x.lb || x.tunnel || !x4_aligned(c))
+		return 0;
+	const size_t fixed = x4_fixed_lds_v4(s0);
+	uint32_t n_cold, P, per;
+	if (!cold_hist_parts(with_lds_hot(s0, fixed < X4_LDS_BUDGET ? (X4_LDS_BUDGET - fixed) / 8u : 0u), n_cold, P, per))
+		return 0;
+	const uint64_t m = std::min<uint64_t>(x.n, PKC_CHUNK);
+	return (size_t)(m + std::min<uint64_t>((m + 4095u) / 4096u, 512u) * 4096u + (64u << 10));
 }
 
 /* The snapshot a launch sees with at most `max_hot` LDS counter slots: hits
@@ -4131,6 +4352,13 @@ static hipError_t launch_x4(const cgpu_snapshot &s0, const cls_args &a, hipStrea
 	const unsigned res = resident_blocks(kern, NT, lds);
 	/* LDS packed counters: <= 2^22 tuples per workgroup (PK_SHIFT) */
 	const uint64_t chunk = std::min<uint64_t>(PKC_CHUNK, (uint64_t)res << 22);
+	/* the cold-hit log's second pass (k_cold_hist, cold_hist_parts).  Without
+	 * a log (none handed in, or no partitions) the whole launch takes the
+	 * atomic on pk for every cold hit.  Only the plain kernel logs
+	 * (k_classify_x4's LOG). */
+	constexpr bool LOG = !LB && !V6 && FR == 0 && !IPCE && !XDP && !KTUN;
+	uint32_t n_cold, hist_P, hist_per;
+	const bool use_log = cold_hist_parts(s, n_cold, hist_P, hist_per) && LOG && a.lg.p;
 	for (uint64_t off = 0; off < a.n; off += chunk) {
 		cls_args c = a;
 		c.cc_n = cc_n;
@@ -4162,8 +4390,29 @@ static hipError_t launch_x4(const cgpu_snapshot &s0, const cls_args &a, hipStrea
 		if (KTUN)
 			tc.tunnel += off;
 		const unsigned g = (unsigned)std::min<uint64_t>((m + Q * NT - 1) / (Q * NT), res);
+		/* this launch's waves, their counts first in the buffer, then a
+		 * region each: a quarter of the tuples the wave handles (its lanes'
+		 * trips through the grid-stride loop, Q tuples each), or what the
+		 * buffer holds; a multiple of 4 words (k_cold_hist's 16-byte loads) */
+		const uint32_t waves = g * (NT / 64u);
+		const uint64_t trips = ((m + Q - 1) / Q + (uint64_t)g * NT - 1) / ((uint64_t)g * NT);
+		const uint64_t head = ((uint64_t)waves + 63u) & ~(uint64_t)63u;
+		c.log_region = 0u;
+		if (use_log && a.lg.words > head) {
+			const uint64_t want = (trips * 64u * Q / 4u + 3u) & ~(uint64_t)3u;
+			const uint64_t fits = ((a.lg.words - head) / waves) & ~(uint64_t)3u;
+			c.log_region = (uint32_t)std::min<uint64_t>(want, fits);
+			c.log_n = a.lg.p;
+			c.log = a.lg.p + head;
+		}
 		hipLaunchKernelGGL((k_classify_x4<NT, true, Q, 1, LB, V6, FR, IPCE, XDP, KTUN>), dim3(g), dim3(NT), lds, st, s,
 				   c, a.pk, fx, tc);
+		if (c.log_region) {
+			/* one workgroup per CU or so, none without a wave to read */
+			const uint32_t R = std::max<uint32_t>(1u, std::min<uint32_t>(res / hist_P, waves));
+			hipLaunchKernelGGL((k_cold_hist<NT>), dim3(hist_P * R), dim3(NT), (size_t)hist_per * 8u, st, a.pk,
+					   c.log, c.log_n, waves, c.log_region, s.hot_slots, n_cold, hist_per, R);
+		}
 		if (s.cold_hi) {
 			const unsigned ug = std::min<unsigned>((s.cold_hi + 255) / 256, 1024);
 			hipLaunchKernelGGL(k_unpack, dim3(ug), dim3(256), 0, st, a.delta, a.pk, 0u, s.cold_hi);
@@ -4175,8 +4424,9 @@ static hipError_t launch_x4(const cgpu_snapshot &s0, const cls_args &a, hipStrea
 /* The context's cgpu_config.schedule selects the schedule (every schedule
  * computes the reference's results, tests/test_gpu_parity.py):
  *   default: k_classify_x4 -- four tuples per lane, vector column loads, LDS
- *      hot counters + one packed atomic per cold hit, resident grid (needs
- *      aligned columns, else the per-lane kernel)
+ *      hot counters + one logged word per cold hit, summed by k_cold_hist
+ *      (CGPU_SCHED_NO_COLD_LOG: one packed atomic per cold hit), resident
+ *      grid (needs aligned columns, else the per-lane kernel)
  *   CGPU_SCHED_PER_LANE: one tuple per lane, LDS hot counters
  *   CGPU_SCHED_GLOBAL_CTR: global atomics for every hit, 256-thread workgroups */
 template <int V6, bool TUN = false>
@@ -4239,6 +4489,7 @@ hipError_t launch_classify_v4(const cgpu_snapshot &s, const classify_v4_args &x,
 	cls_args c{x.saddr, x.daddr, x.dport, x.proto, x.flags, x.len, x.ep, x.verdict, x.identity,
 		   x.stage, x.delta, x.n, x.pk, x.lb, x.sport, x.hash};
 	c.xdp = x.lb ? x.xdp : 0;
+	c.lg = x.log;
 	if (x.tunnel)
 		return launch_classify<0, true>(s, c, st, tun_args{*x.tun, x.tunnel, nullptr});
 	return launch_classify<0>(s, c, st);

@@ -10,6 +10,13 @@
 #include "tables.h"
 #include "../../include/cgpu.h"
 
+/* The cold-hit log of a stream's packed accumulator (k_classify_x4 appends,
+ * k_cold_hist sums it into pk): `words` u32 of device memory owned by the
+ * stream's pk buffer, or {nullptr, 0} (every cold hit is an atomic on pk). */
+struct pk_log {
+	uint32_t *p;
+	uint64_t words;
+};
 struct classify_v4_args {
 	const uint32_t *saddr, *daddr;
 	const uint16_t *dport;
@@ -32,9 +39,16 @@ struct classify_v4_args {
 	 * tunnel tables `tun` */
 	uint32_t *tunnel;
 	const ipc_tun *tun;
+	/* the stream's cold-hit log (only the plain kernel logs: no service
+	 * step, no tunnel output) */
+	pk_log log;
 };
 
 hipError_t launch_classify_v4(const cgpu_snapshot &s, const classify_v4_args &a, hipStream_t st);
+/* bytes of log the call `a` wants, 0 when launch_classify_v4 would not use
+ * one (a smaller log is used as far as it goes: entries that do not fit take
+ * the atomic) */
+size_t x4_log_bytes(const cgpu_snapshot &s, const classify_v4_args &a);
 
 struct classify_v6_args {
 	const uint8_t *saddr16, *daddr16;

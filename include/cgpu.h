@@ -206,6 +206,26 @@ typedef struct cgpu_config {
 #define CGPU_SCHED_FRAMES_SPLIT 8u /* classify_frames, 64-byte slots: a header pass writes tuple columns, then the classify pass (default: one fused kernel) */
 /* bits 4-5: v6 prefilter LDS staging mode + 1 (0 = the deepest that fits) */
 #define CGPU_SCHED_PF6_LDS(mode) ((((uint32_t)(mode)) + 1u) << 4)
+/* cgpu_classify_v4 and cgpu_classify_v4_host (x4 schedule, no tunnel output)
+ * without the cold-hit log: a hit on a counter slot past the LDS hot slots
+ * that the LDS cold-slot cache did not take is one global atomic, deferred
+ * behind the next tuples' column loads.  By default those two calls append
+ * such a hit to a per-stream log with plain stores and a second kernel sums
+ * the log after the classify kernel; a hit that finds its wave's part of the
+ * log full takes the atomic.  A launch takes the atomic path for every such
+ * hit, exactly as with this bit, when the cold slots need more than 8
+ * LDS-sized partitions (about 160k slots) or their count does not fit the
+ * log entry's 21 bits.  No other call logs: the service, cascade, IPv6,
+ * tunnel and frames calls always use the atomics (the second kernel measured
+ * more than the log saved them).
+ * Memory: a stream that logs owns a log of one byte per tuple of its largest
+ * call (at most 64 MiB, plus about 2 MiB), allocated by the first such call,
+ * grown by a larger one after the stream's earlier launches finished, and
+ * freed with the stream's packed counters (cgpu_stream_release, context
+ * destroy, the recycling past 16 streams).  A call that takes the atomic
+ * path allocates none.  As for those counters, the calls on one stream are
+ * made from one thread at a time. */
+#define CGPU_SCHED_NO_COLD_LOG 64u
 /* bits 8-13: conntrack group-key radix sort bits (8..32; 0 = 24) */
 #define CGPU_SCHED_CT_SORT_BITS(b) (((uint32_t)(b)) << 8)
 

@@ -3,7 +3,7 @@ product library: these builds drop work and give wrong counters).
 
     python tools/diag_ab.py build            # in the dev container: tools/_diag/*.so
     python tools/diag_ab.py run [variants]   # on the GPU box
-    (CGPU_AB_CONFIG = gpu (config 2, default) / pf6 (config 3) / v6 / ct / ct6 / ctlb / ctlb6)
+    (CGPU_AB_CONFIG = gpu (config 2, default) / pf6 (config 3) / v6 / ct / ct6 / ctlb / ctlb6;\n     CGPU_AB_SCHED = cgpu_config.schedule for gpu / v6 / frames)
 
 Each variant is cilium_amd/csrc compiled with extra -D flags into
 tools/_diag/libcgpu_<name>.so; `run` loads each in turn into the Engine
@@ -284,7 +284,7 @@ def _workload(conf):
         cfg = T.engine_config()
         if os.environ.get("CGPU_AB_HOT"):  # LDS hot counter slots (bench.py --hot-slots)
             cfg["hot_counter_slots"] = int(os.environ["CGPU_AB_HOT"])
-        e = Engine(device=0, **cfg)
+        e = Engine(device=0, **cfg, schedule=int(os.environ.get("CGPU_AB_SCHED", "0")))
         synth.load_engine(e, T)
         return e
     return make, lambda e: (e.classify_v6 if v6 else e.classify_v4)(d, out=out), n
