@@ -724,7 +724,7 @@ def _be16(x):
 ROUTER_IP6 = bytes([0xbe, 0xef, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 0, 1, 0, 0])
 
 
-def make_frames(rng, n: int, width: int = 256, n_ep: int = 5, addr4=None, edge: bool = True):
+def make_frames(rng, n: int, width: int = 256, n_ep: int = 5, addr4=None, edge: bool = True, addr6=None):
     """Diverse Ethernet frames for the frame-path parity tests (vectorized).
 
     Mix: IPv4 (options, ihl < 5, every frag_off class, TCP/UDP/ICMP/other,
@@ -734,7 +734,9 @@ def make_frames(rng, n: int, width: int = 256, n_ep: int = 5, addr4=None, edge: 
     length (edge=True also makes frames shorter than an Ethernet header).
     Returns dict data (n, width) u8, len u32, flags u8 (egress bit), ep u16;
     len may exceed what a narrower slot stores.  addr4: optional pool of
-    network-order u32 addresses to draw v4 addresses from.
+    network-order u32 addresses to draw v4 addresses from.  addr6: optional
+    (m, 16) uint8 pool: 90% of the IPv6 destinations and of the IPv6 sources
+    that are not the endpoint's come from it (None draws nothing from rng).
     """
     D = rng.integers(0, 256, (n, width), dtype=np.uint8)
     egress = rng.random(n) < 0.5
@@ -805,8 +807,15 @@ def make_frames(rng, n: int, width: int = 256, n_ep: int = 5, addr4=None, edge: 
     chain = rng.choice(EXT_TYPES, (m, 6))
     D[r6, 14] = 0x60
     sa6 = rng.integers(0, 256, (m, 16), dtype=np.uint8)
-    sa6[egress[r6] & (rng.random(m) < 0.9)] = np.frombuffer(LXC_IP6, np.uint8)
+    lxc6 = egress[r6] & (rng.random(m) < 0.9)
+    sa6[lxc6] = np.frombuffer(LXC_IP6, np.uint8)
     D[r6, 22:38] = sa6
+    if addr6 is not None and len(addr6):
+        pool = np.asarray(addr6, np.uint8).reshape(-1, 16)
+        src = (rng.random(m) < 0.9) & ~lxc6
+        dst = rng.random(m) < 0.9
+        D[r6[src], 22:38] = pool[rng.integers(0, len(pool), int(src.sum()))]
+        D[r6[dst], 38:54] = pool[rng.integers(0, len(pool), int(dst.sum()))]
     first = np.where(next_chain > 0, chain[:, 0], proto)
     D[r6, 20] = first
     off = np.full(m, 54, np.int64)

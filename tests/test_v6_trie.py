@@ -4,8 +4,13 @@ a commit does and answers lookups with its host restatement of the device
 walk (cgpu_diag_ipc6_trie, a test hook outside include/cgpu.h); the answers
 must equal the restatement's ipcache LPM (oracle/cgpu_oracle.c
 or_ipcache_lookup, pinned by tests/golden/classify_v6.npz), address by
-address.  The GPU tests (test_gpu_parity / test_gpu_fullsize v6 cases) check
-the device walk itself.  Shapes: the config-v6 table, a /32 too dense for
+address.  The device walks themselves (v6_lookup, v6t_lookup_q staged and
+unstaged, the pre-pass, the frames and conntrack forms) run over the same
+narrow / wide / sparse tables (v6_trie_cases.py) in test_gpu_v6_trie.py; the
+v6 cases of test_gpu_parity / test_gpu_fullsize only meet tables of random
+addresses (no long node, hardly a /64 list of several prefixes).  The
+conditions that make those three tables hard are asserted here, without a
+device.  Shapes: the config-v6 table, a /32 too dense for
 64 sub-range lines (the binary-searched long node), boundaries at both ends
 of a /32 (a window of the whole range), /64s with several nested or disjoint
 /65+ prefixes (lists), static-part entries and ::/0 under everything, /17../32
@@ -15,9 +20,12 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import v6_trie_cases as VC
 from cilium_amd import _abi, layouts as L, synth
+from v6_trie_cases import edge_table, keys_of, probes
 
 V6T_LONG = 7
+V6T_LDS_B24 = 96  # kernels.hip: b24 blocks the x4 walk stages in LDS at most
 
 
 def trie(keys, labels, addrs):
@@ -53,34 +61,6 @@ def oracle_labels(keys, labels, addrs):
     return out
 
 
-def keys_of(addr, plen, static=False):
-    k = np.zeros(len(plen), L.IPCACHE_KEY)
-    k["family"] = L.ENDPOINT_KEY_IPV6
-    k["prefixlen"] = np.asarray(plen) + (0 if static else L.IPCACHE_STATIC_PREFIX)
-    k["ip"] = addr
-    return k
-
-
-def probes(addr, plen, rng, n_rand):
-    """Every prefix's first and last address and their outside neighbours,
-    random addresses inside prefixes and under their /16s."""
-    a = np.asarray(addr, np.uint8)
-    m = synth.MASK6[np.asarray(plen)]
-    lo, hi = a & m, (a & m) | ~m
-    out = [lo, hi]
-    M = (1 << 128) - 1
-    for x, d in ((lo, -1), (hi, 1)):
-        v = [((int.from_bytes(r.tobytes(), "big") + d) & M).to_bytes(16, "big") for r in x]
-        out.append(np.frombuffer(b"".join(v), np.uint8).reshape(-1, 16))
-    pi = rng.integers(0, len(a), n_rand)
-    r = rng.integers(0, 256, (n_rand, 16), dtype=np.uint8)
-    out.append((a[pi] & m[pi]) | (r & ~m[pi]))
-    r2 = rng.integers(0, 256, (n_rand, 16), dtype=np.uint8)
-    r2[:, :2] = a[pi, :2]
-    out.append(r2)
-    return np.concatenate(out)
-
-
 def check(keys, labels, addrs):
     got, st = trie(keys, labels, addrs)
     exp = oracle_labels(keys, labels, addrs)
@@ -99,84 +79,6 @@ def test_trie_config_v6_table():
     assert st["nodes"] > 100 and st["h64"] > 1000
 
 
-def edge_table():
-    rng = np.random.Generator(np.random.PCG64(62))
-    addr, plen, lab = [], [], []
-
-    def put(a, n, lb):
-        a = np.array(a, np.uint8)
-        addr.append(a & synth.MASK6[n])
-        plen.append(n)
-        lab.append(lb)
-    base = np.zeros(16, np.uint8)
-    # a /32 too dense for 64 sub-range lines: 1500 /64s (3000 boundaries)
-    d = base.copy()
-    d[:4] = [0x20, 0x01, 0x0d, 0xb8]
-    put(d, 32, 1001)
-    for i in range(1500):
-        x = d.copy()
-        x[4:8] = rng.integers(0, 256, 4, dtype=np.uint8)
-        put(x, 64, 2000 + i)
-    # boundaries at both ends of a /32, nested inside a /24 and a /20
-    e = base.copy()
-    e[:4] = [0x20, 0x01, 0x0e, 0x77]
-    put(e, 20, 1101)
-    put(e, 24, 1102)
-    lo = e.copy()
-    put(lo, 48, 1103)
-    hi = e.copy()
-    hi[4:8] = 0xFF
-    put(hi, 64, 1104)
-    mid = e.copy()
-    mid[4:6] = [0x80, 0x00]
-    put(mid, 33, 1105)
-    put(mid, 40, 1106)
-    # /64s with nested and disjoint /65+ prefixes (lists) and one inline
-    for j in range(40):
-        s = base.copy()
-        s[:8] = [0x20, 0x01, 0x0f, 0x00, 0x00, j, 0x12, 0x34]
-        put(s, 64, 3000 + j)
-        t = s.copy()
-        t[8:] = rng.integers(0, 256, 8, dtype=np.uint8)
-        put(t, 96, 3100 + j)
-        put(t, 112, 3200 + j)
-        put(t, 128, 3300 + j)
-        if j % 2:
-            u = s.copy()
-            u[8:] = rng.integers(0, 256, 8, dtype=np.uint8)
-            put(u, 128, 3400 + j)
-            put(u, 65, 3500 + j)
-        if j % 5 == 0:
-            v = s.copy()
-            v[8:] = 0xFF
-            put(v, 128, 3600 + j)  # ends at the /64's last address
-    inl = base.copy()
-    inl[:8] = [0x20, 0x01, 0x0f, 0x01, 0, 0, 0, 1]
-    put(inl, 100, 3700)  # a /64 whose only /65+ prefix is inline
-    # /65+ only under a /32 (no /33../64): a deep node of one line
-    o = base.copy()
-    o[:4] = [0x20, 0x01, 0x0f, 0x02]
-    o[8:] = rng.integers(0, 256, 8, dtype=np.uint8)
-    put(o, 128, 3800)
-    # /17../32 expansion around a /48, tombstones
-    f = base.copy()
-    f[:6] = [0x20, 0x01, 0x0a, 0x0b, 0x0c, 0x0d]
-    put(f, 17, 4001)
-    put(f, 23, 4002)
-    put(f, 29, 0)  # tombstone (sec_label 0: a match that shadows)
-    put(f, 31, 4004)
-    put(f, 48, 4005)
-    put(f, 56, 0)
-    # ::/0 and two static-part entries (rank below /0)
-    put(base, 0, 2)
-    keys = keys_of(np.array(addr), plen)
-    st_keys = np.zeros(2, L.IPCACHE_KEY)
-    st_keys["family"] = L.ENDPOINT_KEY_IPV6
-    st_keys["prefixlen"] = [0, 31]
-    return (np.concatenate([keys, st_keys]), np.array(lab + [7, 8], np.uint32),
-            np.array(addr), np.array(plen), rng)
-
-
 def test_trie_edge_shapes():
     keys, labels, addr, plen, rng = edge_table()
     addrs = probes(addr, plen, rng, 20_000)
@@ -184,6 +86,90 @@ def test_trie_edge_shapes():
     assert st["long"] >= 1           # the dense /32
     assert st["lists"] >= 20         # nested / disjoint /65+ in one /64
     assert st["h64"] > st["lists"]   # and inline records
+
+
+@pytest.fixture(scope="module", params=sorted(VC.CASES))
+def case_stats(request):
+    """Every shared table: the host walk equals the restatement on its probe
+    addresses; -> (case, trie statistics, restatement rows)."""
+    c = VC.CASES[request.param]()
+    st = check(c.keys, c.labels, c.addrs)
+    return c, st, VC.restate(c)
+
+
+def test_case_probe_sets(case_stats):
+    """What the device tests rely on: ragged, at most 40k, and the
+    restatement's batch lookup says what its map lookup says."""
+    c, _, rows = case_stats
+    assert len(c.addrs) % 4 != 0 and len(c.addrs) <= 40_000
+    exp = oracle_labels(c.keys, c.labels, c.addrs[::7])
+    np.testing.assert_array_equal(np.where(rows[::7, 0] == 1, rows[::7, 1], 0xFFFFFFFF), exp)
+    hit = rows[:, 0] == 1
+    assert len(np.unique(rows[hit, 2])) > 100  # a tunnel word per prefix
+    assert (hit & (rows[:, 1] == 0)).sum() >= 10  # tombstones are matches
+
+
+def test_case_shapes(case_stats):
+    """The conditions on the inputs (stated for the tables, not for the
+    library's answers): which trie levels and arms the probes reach."""
+    c, st, rows = case_stats
+    print(c.name, st)
+    w0, w1 = c.h64_keys()
+    assert st["h64"] == len(w0)  # one record per /64 with /65+ prefixes
+    if c.name == "narrow":
+        assert 1 <= st["b24"] <= V6T_LDS_B24 and st["long"] >= 1
+        return
+    if c.name == "wide":
+        assert st["b24"] > V6T_LDS_B24 and st["long"] >= 1 and st["lists"] >= 20
+        return
+    miss = (rows[:, 0] == 0).mean()
+    n_out = int(c.outside().sum())
+    slots = st["slots"]
+    assert slots & (slots - 1) == 0
+    per_home = np.bincount(VC.mix32(w0, w1) & np.uint32(slots - 1), minlength=slots)
+    indirect = np.unique(rows[(rows[:, 0] == 1) & (rows[:, 1] >= 1 << 30), 1])
+    print("miss", miss, "outside", n_out, "homes >= 2", (per_home >= 2).sum(), ">= 3", (per_home >= 3).sum(),
+          "indirect", len(indirect))
+    assert 0.05 <= miss <= 0.60
+    assert n_out >= 100
+    assert len(w0) >= 3000
+    assert (per_home >= 2).sum() >= 50 and (per_home >= 3).sum() >= 5
+    assert len(indirect) >= 20
+
+
+def test_frames_addr6_pool():
+    """synth.make_frames(addr6=): IPv6 frames carry pool addresses (about
+    90 % of the destinations, of the sources all but the endpoint's own);
+    an empty pool draws nothing, so the frames are those of addr6=None."""
+    pool = VC.narrow().addrs[:5000]
+    mk = lambda **kw: synth.make_frames(np.random.Generator(np.random.PCG64(9)), 20_000, width=128, **kw)  # noqa: E731
+    f, f0, fe = mk(addr6=pool), mk(), mk(addr6=pool[:0])
+    assert all(np.array_equal(f0[k], fe[k]) for k in f0)
+    D = f["data"]
+    v6 = (D[:, 12] == 0x86) & (D[:, 13] == 0xDD)
+    keys = set(map(bytes, pool))
+    d_in = np.array([bytes(r) in keys for r in D[v6, 38:54]])
+    s_in = np.array([bytes(r) in keys for r in D[v6, 22:38]])
+    lxc = (D[v6, 22:38] == np.frombuffer(synth.LXC_IP6, np.uint8)).all(1)
+    assert v6.sum() > 4000 and 0.8 < d_in.mean() < 0.95
+    assert not (s_in & lxc).any() and 0.8 < s_in[~lxc].mean() < 0.95
+    assert np.array_equal(f["data"][~v6], f0["data"][~v6])  # the other frames are unchanged
+
+
+def test_mix32_mirror():
+    """The numpy mix32 against values worked out with Python integers."""
+    def ref(a, b):
+        m = (1 << 64) - 1
+        h = ((b << 32 | a) * 0x9E3779B97F4A7C15) & m
+        h ^= h >> 29
+        h = (h * 0xBF58476D1CE4E5B9) & m
+        h ^= h >> 32
+        return h & 0xFFFFFFFF
+    rng = np.random.Generator(np.random.PCG64(5))
+    a = rng.integers(0, 1 << 32, 200, dtype=np.uint64).astype(np.uint32)
+    b = rng.integers(0, 1 << 32, 200, dtype=np.uint64).astype(np.uint32)
+    a[:3], b[:3] = [0, 0xFFFFFFFF, 1], [0, 0xFFFFFFFF, 0]
+    assert VC.mix32(a, b).tolist() == [ref(int(x), int(y)) for x, y in zip(a, b)]
 
 
 def test_trie_static_only_and_empty():
