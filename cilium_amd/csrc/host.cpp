@@ -495,6 +495,7 @@ struct PolBuild {
 	std::vector<pol_slot> slots;
 	uint32_t mask = 0;
 	size_t count = 0;
+	uint64_t relocations = 0; /* keys moved by insert (cgpu_diag_pol_tables), counted only */
 	bool used(uint32_t i) const { return (slots[i & mask].ctr & POL_CTR_MASK) != POL_CTR_EMPTY; }
 	/* place one key; false when no free slot can be brought into its
 	 * neighbourhood.  Hopscotch insertion: the nearest free slot past the
@@ -533,6 +534,7 @@ struct PolBuild {
 					slots[h2].ctr = (slots[h2].ctr & ~(1u << (POL_HOP_SHIFT + o))) | (1u << (POL_HOP_SHIFT + j));
 					d -= j - o;
 					moved = true;
+					relocations++;
 					break;
 				}
 			}
@@ -1901,6 +1903,7 @@ struct BuildState {
 	ipc_tun tun{};
 	uint64_t ipc_builds = 0, ipc_patched = 0; /* IPv4 full builds / patch commits (cgpu_diag_ipc_commits) */
 	bool pol_ok = false;
+	uint64_t pol_builds = 0, pol_patched = 0; /* policy full builds / patch commits (cgpu_diag_pol_tables) */
 	PolBuild pol;
 	PgBuild pg;
 	uint64_t sum[G_N] = {};
@@ -4030,8 +4033,9 @@ static int commit_ipc(cgpu_ctx *c, CommitIn &in, cgpu_snapshot &s, DevBufP &buf)
 	return 0;
 }
 
-/* group POL: the policy hash and its groups */
-static int commit_pol(cgpu_ctx *c, CommitIn &in, cgpu_snapshot &s, DevBufP &buf)
+/* the host images of group POL brought up to the captured mirror: the
+ * captured changes patched in place, or a full build (also cgpu_diag_pol_tables) */
+static void compile_pol(cgpu_ctx *c, CommitIn &in)
 {
 	BuildState &b = c->b;
 	bool full = in.pol_full;
@@ -4058,7 +4062,17 @@ static int commit_pol(cgpu_ctx *c, CommitIn &in, cgpu_snapshot &s, DevBufP &buf)
 		b.pol.build(in.pol_keys);
 		b.pg.build(in.pol_keys);
 		b.pol_ok = true;
+		b.pol_builds++;
+	} else {
+		b.pol_patched++;
 	}
+}
+
+/* group POL: the policy hash and its groups */
+static int commit_pol(cgpu_ctx *c, CommitIn &in, cgpu_snapshot &s, DevBufP &buf)
+{
+	BuildState &b = c->b;
+	compile_pol(c, in);
 	Arena ar;
 	const size_t o_p = ar.add(b.pol.slots.data(), b.pol.slots.size() * sizeof(pol_slot));
 	const size_t o_g = ar.add(b.pg.slots.data(), b.pg.slots.size() * sizeof(uint4));
@@ -4837,29 +4851,22 @@ static uint32_t leaf_value(const std::vector<uint32_t> &vals, uint32_t e)
 	return (e & DIR_TAG_MASK) == DIR_TAG_INDIRECT ? vals[e & DIR_PAYLOAD_MASK] : e & DIR_PAYLOAD_MASK;
 }
 
-/* Test hook (not part of the drop-in boundary, no header): the ipcache's
- * identity and tunnel tables compiled as cgpu_commit compiles them with
- * cgpu_config.ipcache_tunnel set, on a host-only context, and walked on the
- * host as the kernels walk them.  The first n_first entries are one commit,
- * the other n - n_first a second one (which patches in place where a commit
- * would); del[i] != 0 (del may be NULL) deletes key i instead of updating it.
- * addrs: m network-order u32 (v6 = 0) or m x 16 bytes.  out[3 j ..]:
- * {found, sec_label, tunnel_endpoint} of the longest match, the ipcache_lookup4
- * / 6 answer (eps.h:56-80).  commits (may be NULL): {IPv4 full builds, commits
- * that patched}. */
-CGPU_EXPORT int cgpu_diag_ipc_tunnel(const cgpu_ipcache_key *keys, const cgpu_remote_endpoint_info *vals,
-				     const uint8_t *del, size_t n, size_t n_first, const void *addrs, size_t m,
-				     int v6, uint32_t *out, uint64_t *commits)
+/* The ipcache of a fresh host-only context (cgpu_config.ipcache_tunnel set)
+ * compiled as two commits compile it: entries [0, n_first) then [n_first, n),
+ * del[i] != 0 (del may be NULL) deleting key i.  *out is NULL only when no
+ * context could be made; else the caller destroys it, whatever is returned. */
+static int diag_ipc_compile(const cgpu_ipcache_key *keys, const cgpu_remote_endpoint_info *vals,
+			    const uint8_t *del, size_t n, size_t n_first, cgpu_ctx **out)
 {
-	if ((n && (!keys || !vals)) || (m && (!addrs || !out)) || n_first > n)
-		return fail(-EINVAL, "null argument");
 	cgpu_config cfg;
 	cgpu_config_default(&cfg);
 	cfg.ipcache_tunnel = 1;
 	cfg.ipcache_max = (uint32_t)std::max<size_t>(n, 1);
 	cgpu_ctx *c = nullptr;
+	*out = nullptr;
 	if (int r = cgpu_ctx_create(&cfg, -1, &c))
 		return r;
+	*out = c;
 	int rc = 0;
 	for (int phase = 0; phase < 2 && !rc; phase++) {
 		const size_t lo = phase ? n_first : 0, hi = phase ? n : n_first;
@@ -4878,6 +4885,29 @@ CGPU_EXPORT int cgpu_diag_ipc_tunnel(const cgpu_ipcache_key *keys, const cgpu_re
 		}
 		compile_ipc(c->b, in);
 	}
+	return rc;
+}
+
+/* Test hook (not part of the drop-in boundary, no header): the ipcache's
+ * identity and tunnel tables compiled as cgpu_commit compiles them with
+ * cgpu_config.ipcache_tunnel set, on a host-only context, and walked on the
+ * host as the kernels walk them.  The first n_first entries are one commit,
+ * the other n - n_first a second one (which patches in place where a commit
+ * would); del[i] != 0 (del may be NULL) deletes key i instead of updating it.
+ * addrs: m network-order u32 (v6 = 0) or m x 16 bytes.  out[3 j ..]:
+ * {found, sec_label, tunnel_endpoint} of the longest match, the ipcache_lookup4
+ * / 6 answer (eps.h:56-80).  commits (may be NULL): {IPv4 full builds, commits
+ * that patched}. */
+CGPU_EXPORT int cgpu_diag_ipc_tunnel(const cgpu_ipcache_key *keys, const cgpu_remote_endpoint_info *vals,
+				     const uint8_t *del, size_t n, size_t n_first, const void *addrs, size_t m,
+				     int v6, uint32_t *out, uint64_t *commits)
+{
+	if ((n && (!keys || !vals)) || (m && (!addrs || !out)) || n_first > n)
+		return fail(-EINVAL, "null argument");
+	cgpu_ctx *c = nullptr;
+	int rc = diag_ipc_compile(keys, vals, del, n, n_first, &c);
+	if (!c)
+		return rc;
 	const BuildState &b = c->b;
 	if (!rc && (b.v6.too_big || b.v6T.too_big))
 		rc = -E2BIG;
@@ -4916,6 +4946,162 @@ CGPU_EXPORT int cgpu_diag_ipc_commits(cgpu_ctx *c, uint64_t *out)
 	out[0] = c->b.ipc_builds;
 	out[1] = c->b.ipc_patched;
 	return 0;
+}
+
+/* the shape of every /16 of one compiled lpm16c table: cgpu_diag_ipc4_shapes */
+static void lpmc_shapes(const Lpm16cBuild &t, uint32_t *o)
+{
+	const uint32_t GRP = DIR_TAG_GROUP >> LPMC_KIND_SHIFT;
+	o[0] = (uint32_t)t.dict.size();
+	o[15] = (uint32_t)t.nodes.size();
+	if (t.x16.empty())
+		return;
+	for (uint32_t p = 0; p < 65536; p++) {
+		const uint32_t *q = &t.x16[(size_t)p * 4];
+		if (!(q[3] & LPMC_OVERFLOW)) {
+			/* neighbouring runs differ in their leaf, so in their code: a
+			 * repeated code is an unused run start (0xFFFF may be a real one) */
+			const uint64_t v = ((uint64_t)q[3] << 32) | q[2];
+			uint32_t starts = 0;
+			for (uint32_t i = 0; i < 4; i++)
+				starts += ((v >> (12u * i)) & 0xFFFu) != ((v >> (12u * (i + 1))) & 0xFFFu);
+			o[1 + starts]++;
+			continue;
+		}
+		const uint32_t e = q[0];
+		if ((e & DIR_TAG_MASK) != DIR_TAG_GROUP) {
+			o[6]++;
+			continue;
+		}
+		const uint32_t kind = (e >> LPMC_KIND_SHIFT) & 3u;
+		o[7 + kind]++;
+		if (kind != 3u)
+			continue;
+		const uint32_t *a = &t.nodes[(size_t)(e & LPMC_OFF_MASK) * 4u];
+		for (uint32_t j = 0; j < 256; j++)
+			if ((a[j] >> LPMC_KIND_SHIFT & ~3u) == GRP)
+				o[11 + ((a[j] >> LPMC_KIND_SHIFT) & 3u)]++;
+	}
+}
+
+/* Test hook (no header): the shapes of the IPv4 ipcache tables (tables.h
+ * lpm16c) compiled as cgpu_diag_ipc_tunnel compiles them (same arguments up to
+ * n_first).  out[0..15]: the identity table, out[16..31]: the tunnel table:
+ *   [0] n_dict; the number of /16s that are [1..5] inline with 0..4 run
+ *   starts, [6] overflow with a plain leaf, [7..9] overflow with a run node of
+ *   kind 0..2, [10] overflow with an array; below those arrays, the number of
+ *   [11..13] byte-level run nodes of kind 0..2 and [14] 256-leaf arrays;
+ *   [15] words of `nodes`.
+ * commits (may be NULL): {IPv4 full builds, commits that patched}. */
+CGPU_EXPORT int cgpu_diag_ipc4_shapes(const cgpu_ipcache_key *keys, const cgpu_remote_endpoint_info *vals,
+				      const uint8_t *del, size_t n, size_t n_first, uint32_t *out, uint64_t *commits)
+{
+	if ((n && (!keys || !vals)) || !out || n_first > n)
+		return fail(-EINVAL, "null argument");
+	cgpu_ctx *c = nullptr;
+	const int rc = diag_ipc_compile(keys, vals, del, n, n_first, &c);
+	if (!c)
+		return rc;
+	memset(out, 0, 32 * sizeof(uint32_t));
+	if (!rc) {
+		lpmc_shapes(c->b.lc, out);
+		lpmc_shapes(c->b.lcT, out + 16);
+	}
+	if (commits) {
+		commits[0] = c->b.ipc_builds;
+		commits[1] = c->b.ipc_patched;
+	}
+	cgpu_ctx_destroy(c);
+	return rc;
+}
+
+/* Test hook (no header): the policy table and its groups (tables.h pol_table,
+ * pol_groups) built as cgpu_commit builds them, on a host-only context.  Rows
+ * [0, n_first) of {eps, keys, entries} are one commit, the other n - n_first a
+ * second one, which patches in place where a commit would; del[i] != 0 (del
+ * may be NULL) deletes key i instead of updating it.  rows[4 i ..], for key i
+ * as the second commit leaves it: {home slot, the slot it is stored in, home
+ * slot of its group, the group's slot}; the group words are ~0 for a key that
+ * is not groupable, all four for a key no longer present.  stats[0..7]: the
+ * key table's mask, the group table's mask, hopscotch relocations of the
+ * first commit and of the second, full builds, commits that patched, keys and
+ * groups stored. */
+CGPU_EXPORT int cgpu_diag_pol_tables(const uint32_t *eps, const cgpu_policy_key *keys,
+				     const cgpu_policy_entry *entries, const uint8_t *del, size_t n,
+				     size_t n_first, uint32_t *rows, uint64_t *stats)
+{
+	if ((n && (!eps || !keys || !entries || !rows)) || !stats || n_first > n)
+		return fail(-EINVAL, "null argument");
+	cgpu_config cfg;
+	cgpu_config_default(&cfg);
+	cgpu_ctx *c = nullptr;
+	if (int r = cgpu_ctx_create(&cfg, -1, &c))
+		return r;
+	int rc = 0;
+	uint64_t reloc[2] = {0, 0};
+	for (int phase = 0; phase < 2 && !rc; phase++) {
+		const size_t lo = phase ? n_first : 0, hi = phase ? n : n_first;
+		if (phase && lo == hi)
+			break;
+		for (size_t i = lo; i < hi && !rc; i++)
+			rc = del && del[i] ? cgpu_policy_delete(c, eps[i], &keys[i])
+					   : cgpu_policy_update(c, eps[i], &keys[i], &entries[i], CGPU_ANY);
+		if (rc)
+			break;
+		CommitIn in;
+		in.cfg = c->cfg;
+		{
+			std::lock_guard<std::mutex> g(c->mu);
+			capture_pol(c, in, c->b);
+		}
+		const uint64_t before = c->b.pol.relocations;
+		compile_pol(c, in);
+		reloc[phase] = c->b.pol.relocations - before;
+	}
+	BuildState &b = c->b;
+	for (size_t i = 0; i < n && !rc; i++) {
+		uint32_t *r = rows + 4 * i;
+		r[0] = r[1] = r[2] = r[3] = ~0u;
+		const uint64_t k64 = pol_key64(&keys[i]);
+		PolEntry pe;
+		{
+			std::lock_guard<std::mutex> g(c->mu);
+			auto it = c->pol[eps[i]].find(k64);
+			if (it == c->pol[eps[i]].end())
+				continue;
+			pe = it->second;
+		}
+		const PolKey k = pol_key_of(eps[i], k64, pe);
+		const uint32_t home = pol_hash(k.lo, k.hi, eps[i]) & b.pol.mask;
+		const uint32_t hop = b.pol.slots[home].ctr >> POL_HOP_SHIFT;
+		r[0] = home;
+		for (uint32_t d = 0; d < POL_HOP; d++) {
+			const pol_slot &sl = b.pol.slots[(home + d) & b.pol.mask];
+			if (((hop >> d) & 1u) && sl.key_lo == k.lo && sl.key_hi == k.hi && (sl.ep_proxy & 0xFFFFu) == eps[i])
+				r[1] = (home + d) & b.pol.mask;
+		}
+		if (r[1] == ~0u)
+			rc = fail(-ENOENT, "policy key %zu of the mirror is not in the table", i);
+		if (!PgBuild::groupable(k))
+			continue;
+		const int64_t g = b.pg.find(k.lo, PgBuild::ep_dir(k), false);
+		if (g < 0) {
+			rc = fail(-ENOENT, "the group of policy key %zu is not in the table", i);
+			continue;
+		}
+		r[2] = pg_hash(k.lo, PgBuild::ep_dir(k)) & b.pg.mask;
+		r[3] = (uint32_t)g;
+	}
+	stats[0] = b.pol.mask;
+	stats[1] = b.pg.mask;
+	stats[2] = reloc[0];
+	stats[3] = reloc[1];
+	stats[4] = b.pol_builds;
+	stats[5] = b.pol_patched;
+	stats[6] = b.pol.count;
+	stats[7] = b.pg.count;
+	cgpu_ctx_destroy(c);
+	return rc;
 }
 
 CGPU_EXPORT int cgpu_counter_layout_checksum(cgpu_ctx *c, uint64_t *sum)

@@ -486,27 +486,9 @@ def test_unaligned_columns_take_scalar_schedule(torch_cuda, cfg1, monkeypatch):
 
 
 def _lpm_shapes_tables(rng):
-    """ipcache contents that force every compressed-LPM shape (tables.h
-    lpm16c): uniform /16 leaves, 16/32/64-byte run nodes, /16 arrays whose
-    /24 entries are leaves, byte-level run nodes or 256-leaf arrays, run
-    starts at the last address of a /16, tombstones and labels >= 2^30."""
-    cidrs = [("0.0.0.0/0", L.WORLD_ID), ("10.7.0.0/16", L.CLUSTER_ID)]
-    lab = lambda: int(rng.choice([rng.integers(256, 70000), rng.integers(1 << 30, 1 << 32)]))
-    cidrs += [(f"20.1.{16 * i}.0/20", lab()) for i in range(2)]            # kind 0/1 nodes
-    cidrs += [(f"20.2.{3 * i}.0/24", lab()) for i in range(5)]             # kind 2 node
-    cidrs += [(f"20.3.{7 * i}.0/24", lab()) for i in range(11)]            # /16 array of leaves
-    cidrs += [("20.4.255.255/32", lab()), ("20.4.0.0/32", lab()), ("20.5.128.0/17", 0)]
-    cidrs += [(f"20.6.{i}.{j}/32", lab()) for i in range(0, 256, 3) for j in rng.choice(256, 40, replace=False)]
-    cidrs += [(f"20.6.{i}.{16 * j}/28", lab()) for i in range(1, 256, 3) for j in range(0, 16, 5)]
-    cidrs += [(f"20.7.{i}.{4 * j}/30", lab()) for i in range(8) for j in range(0, 64, 2)]
-    cidrs += [("20.8.0.0/16", 0), ("20.8.1.0/24", lab()), ("20.9.0.0/15", lab())]
-    seen, keys, vals = set(), [], []
-    for c, v in cidrs:
-        if c in seen:
-            continue
-        seen.add(c)
-        keys.append(L.ipcache_key(c))
-        vals.append(L.remote_info(v, 0))
+    """cascade_cases.lpm_shapes as key and value arrays"""
+    from cascade_cases import lpm_shapes
+    keys, vals = zip(*lpm_shapes(rng))
     return np.array(keys), np.array(vals)
 
 

@@ -11,6 +11,7 @@ covered by their own files."""
 import numpy as np
 import pytest
 
+from cascade_cases import key_hi as _key_hi, lpm_shapes as _lpm_shapes, pg_bloom as _pg_bloom, pol_hash as _pol_hash
 from cilium_amd import build, layouts as L, synth
 
 pytestmark = pytest.mark.gpu
@@ -83,40 +84,6 @@ def test_several_loop_iterations(torch_cuda, loops_case, sched):
 # --------------------------------------------------------------------------
 # hop neighbourhoods of the policy table
 # --------------------------------------------------------------------------
-def _u64(x):
-    return np.asarray(x).astype(np.uint64)
-
-
-def _pol_hash(lo, hi, ep):
-    """tables.h pol_hash, vectorised"""
-    with np.errstate(over="ignore"):
-        h = ((_u64(hi) << np.uint64(32)) | _u64(lo)) ^ (_u64(ep) * np.uint64(0x9E3779B97F4A7C15))
-        h ^= h >> np.uint64(33)
-        h *= np.uint64(0xff51afd7ed558ccd)
-        h ^= h >> np.uint64(33)
-        h *= np.uint64(0xc4ceb9fe1a85ec53)
-        h ^= h >> np.uint64(33)
-    return (h & np.uint64(0xFFFFFFFF)).astype(np.uint32)
-
-
-def _pg_bloom(dport, proto):
-    """tables.h pg_bloom (mix32 of dport | proto << 16 and 0x3c6ef372)"""
-    with np.errstate(over="ignore"):
-        h = ((np.uint64(0x3c6ef372) << np.uint64(32)) | (_u64(dport) | (_u64(proto) << np.uint64(16)))) \
-            * np.uint64(0x9E3779B97F4A7C15)
-        h ^= h >> np.uint64(29)
-        h *= np.uint64(0xbf58476d1ce4e5b9)
-        h ^= h >> np.uint64(32)
-    h = (h & np.uint64(0xFFFFFFFF)).astype(np.uint32)
-    return (np.uint32(1) << (h & np.uint32(31))) | (np.uint32(1) << ((h >> np.uint32(8)) & np.uint32(31)))
-
-
-def _key_hi(dport_be, proto, egress):
-    """the policy key's upper word as the table stores it"""
-    return _u64(dport_be).astype(np.uint32) | (_u64(proto).astype(np.uint32) << np.uint32(16)) | \
-        (_u64(egress).astype(np.uint32) << np.uint32(24))
-
-
 POL_SLOTS = 1 << 16  # the table the key set below is laid out for (asserted)
 
 
@@ -334,31 +301,6 @@ def test_inactive_lanes(torch_cuda, tables):
 # --------------------------------------------------------------------------
 # every shape of the compressed ipcache table
 # --------------------------------------------------------------------------
-def _lpm_shapes(rng):
-    """ipcache contents that force every compressed-LPM shape (tables.h
-    lpm16c): uniform /16 leaves, inline /16s, 16/32/64-byte run nodes, /16
-    arrays whose /24 entries are leaves, byte-level run nodes or 256-leaf
-    arrays, run starts at the last address of a /16, tombstones, and labels
-    >= 2^30 (leaves that index `vals`)."""
-    def lab():
-        return int(rng.choice([rng.integers(256, 70000), rng.integers(1 << 30, 1 << 32)]))
-    cidrs = [("0.0.0.0/0", L.WORLD_ID), ("10.7.0.0/16", L.CLUSTER_ID)]
-    cidrs += [(f"20.1.{16 * i}.0/20", lab()) for i in range(2)]            # 16- / 32-byte nodes
-    cidrs += [(f"20.2.{3 * i}.0/24", lab()) for i in range(5)]             # 64-byte node
-    cidrs += [(f"20.3.{7 * i}.0/24", lab()) for i in range(11)]            # /16 array of leaves
-    cidrs += [("20.4.255.255/32", lab()), ("20.4.0.0/32", lab()), ("20.5.128.0/17", 0)]
-    cidrs += [(f"20.6.{i}.{j}/32", lab()) for i in range(0, 256, 3) for j in rng.choice(256, 40, replace=False)]
-    cidrs += [(f"20.6.{i}.{16 * j}/28", lab()) for i in range(1, 256, 3) for j in range(0, 16, 5)]
-    cidrs += [(f"20.7.{i}.{4 * j}/30", lab()) for i in range(8) for j in range(0, 64, 2)]
-    cidrs += [("20.8.0.0/16", 0), ("20.8.1.0/24", lab()), ("20.9.0.0/15", lab())]
-    seen, out = set(), []
-    for c, v in cidrs:
-        if c not in seen:
-            seen.add(c)
-            out.append((L.ipcache_key(c), L.remote_info(v, 0)))
-    return out
-
-
 def test_lpm_shapes_in_quads(torch_cuda):
     """Addresses drawn per tuple over the /16s of every shape, so that the
     four tuples of a quad take different paths through the table: inline

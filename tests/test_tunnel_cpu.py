@@ -124,9 +124,12 @@ def test_shadow_case():
 
 
 def _rand_tables(rng, n32=6000):
-    """6000 /32s in 40 /16s with distinct tunnels (more leaves than the 4095
-    dictionary codes, more than 4 runs per /16: overflow nodes), /25../31 under
-    /24s under a /16 (kind-3 arrays, run nodes over the last byte)."""
+    """6000 /32s in 40 /16s with distinct tunnels, /25../31 under /24s under a
+    /16.  As cgpu_diag_ipc4_shapes reports it: all 41 /16s overflow to kind-3
+    arrays (about 150 /32s each), below them byte-level run nodes of every kind
+    and a few 256-leaf arrays.  No /16 is inline-able, so the leaf dictionary
+    holds one code (the empty leaf): a full dictionary and run nodes directly
+    under d16 are cascade_cases.lpm4_full_dict's."""
     ents, seen = [], set()
     tun = rng.permutation(np.arange(1 << 30, (1 << 30) + 4 * n32, dtype=np.uint32))
     p16 = rng.choice(np.arange(0x0B00, 0x0C00), 40, replace=False)
