@@ -92,6 +92,14 @@ class FwdOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("action", "ret", "ifindex", "arg")]
 
 
+class DlvIn(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("action", "arg", "src_label", "src_ep", "dport", "proto", "flags", "len")]
+
+
+class DlvOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("verdict", "identity", "stage")]
+
+
 class Frames(C.Structure):
     _fields_ = [("data", C.c_void_p), ("len", C.c_void_p), ("flags", C.c_void_p),
                 ("ep", C.c_void_p), ("stride", C.c_uint32), ("reserved", C.c_uint32)]
@@ -150,6 +158,8 @@ PROTOS = {
     "cgpu_forward_v4": (i32, [vp, C.POINTER(FwdParams), C.POINTER(FwdIn), sz, C.POINTER(FwdOut), vp]),
     "cgpu_forward_v6": (i32, [vp, C.POINTER(FwdParams), C.POINTER(FwdIn), sz, C.POINTER(FwdOut), vp]),
     "cgpu_forward_table_bytes": (i32, [vp, vp]),
+    "cgpu_deliver_v4": (i32, [vp, C.POINTER(DlvIn), sz, C.POINTER(DlvOut), vp]),
+    "cgpu_deliver_v6": (i32, [vp, C.POINTER(DlvIn), sz, C.POINTER(DlvOut), vp]),
     "cgpu_lb4_update": (i32, [vp, vp, vp, u64]),
     "cgpu_lb4_update_batch": (i32, [vp, vp, vp, sz, u64]),
     "cgpu_lb4_delete": (i32, [vp, vp]),

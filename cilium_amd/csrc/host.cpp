@@ -5424,6 +5424,59 @@ CGPU_EXPORT int cgpu_forward_v6(cgpu_ctx *c, const cgpu_fwd_params *p, const cgp
 	return forward_batch(c, p, in, n, out, 1, stream);
 }
 
+/* local delivery (cgpu.h cgpu_deliver_v4 / _v6): the call's shape is judged
+ * before the context, so a malformed call is -EINVAL everywhere */
+static int deliver_batch(cgpu_ctx *c, const cgpu_dlv_in *in, size_t n, const cgpu_dlv_out *out, int v6,
+			 void *stream)
+{
+	if (!c || !in || !out)
+		return fail(-EINVAL, "null argument");
+	if (n && (!in->action || !in->arg || !in->dport || !in->proto || !in->flags || !in->len || !out->verdict))
+		return fail(-EINVAL, "null column or verdict output");
+	if (n && !in->src_label == !in->src_ep)
+		return fail(-EINVAL, "exactly one of src_label and src_ep is needed");
+	if (((uintptr_t)in->arg | (uintptr_t)in->src_label | (uintptr_t)in->len | (uintptr_t)out->verdict |
+	     (uintptr_t)out->identity) & 3u)
+		return fail(-EINVAL, "4-byte column not 4-byte aligned");
+	if (((uintptr_t)in->src_ep | (uintptr_t)in->dport) & 1u)
+		return fail(-EINVAL, "2-byte column not 2-byte aligned");
+	Pinned P;
+	if (int r = pin(c, stream, P))
+		return r;
+	if (!n)
+		return 0;
+	dlv_args a{};
+	a.action = in->action;
+	a.arg = in->arg;
+	a.src_label = in->src_label;
+	a.src_ep = in->src_ep;
+	a.dport = in->dport;
+	a.proto = in->proto;
+	a.flags = in->flags;
+	a.len = in->len;
+	a.verdict = out->verdict;
+	a.identity = out->identity;
+	a.stage = out->stage;
+	a.delta = P.delta;
+	a.n = n;
+	a.max_ep = std::min<uint32_t>(c->cfg.max_endpoints, 0x10000u);
+	a.v6 = v6;
+	HIP_OR_EIO(launch_deliver(P.snap(), a, (hipStream_t)stream));
+	return 0;
+}
+
+CGPU_EXPORT int cgpu_deliver_v4(cgpu_ctx *c, const cgpu_dlv_in *in, size_t n, const cgpu_dlv_out *out,
+				void *stream)
+{
+	return deliver_batch(c, in, n, out, 0, stream);
+}
+
+CGPU_EXPORT int cgpu_deliver_v6(cgpu_ctx *c, const cgpu_dlv_in *in, size_t n, const cgpu_dlv_out *out,
+				void *stream)
+{
+	return deliver_batch(c, in, n, out, 1, stream);
+}
+
 CGPU_EXPORT int cgpu_forward_table_bytes(cgpu_ctx *c, uint64_t *out)
 {
 	if (!c || !out)

@@ -4040,6 +4040,227 @@ __global__ __launch_bounds__(BLOCK) void k_forward(fwd_tables F, fwd_args a)
 	}
 }
 
+/* Q consecutive elements of a 1 / 2 / 4-byte column from one nontemporal
+ * load of Q * sizeof(T) bytes (p aligned to that), and the store of Q */
+template <int Q, typename T> __device__ __forceinline__ void ld_colq(const T *p, uint32_t (&v)[Q])
+{
+	constexpr int B = Q * (int)sizeof(T);
+	static_assert(B == 2 || B == 4 || B == 8 || B == 16, "one load");
+	uint32_t w[4] = {0u, 0u, 0u, 0u};
+	if constexpr (B == 16) {
+		const uint4 x = ld_x4<true>(p);
+		w[0] = x.x, w[1] = x.y, w[2] = x.z, w[3] = x.w;
+	} else if constexpr (B == 8) {
+		const uint2 x = ld_x2<true>(p);
+		w[0] = x.x, w[1] = x.y;
+	} else if constexpr (B == 4) {
+		w[0] = ld_x1<true>(p);
+	} else {
+		w[0] = ntl(reinterpret_cast<const uint16_t *>(p));
+	}
+#pragma unroll
+	for (int u = 0; u < Q; u++) {
+		if constexpr (sizeof(T) == 4)
+			v[u] = w[u];
+		else if constexpr (sizeof(T) == 2)
+			v[u] = (w[u >> 1] >> (16u * (u & 1))) & 0xFFFFu;
+		else
+			v[u] = (w[0] >> (8u * u)) & 0xFFu;
+	}
+}
+template <int Q, typename T> __device__ __forceinline__ void st_colq(T *p, const uint32_t (&v)[Q])
+{
+	static_assert(sizeof(T) == 4 || sizeof(T) == 1, "verdict / identity / stage");
+	if constexpr (sizeof(T) == 4 && Q == 4) {
+		st_x4<true>(p, v[0], v[1], v[2], v[3]);
+	} else if constexpr (sizeof(T) == 4) {
+		const v2u_t x = {v[0], v[1]};
+		__builtin_nontemporal_store(x, reinterpret_cast<v2u_t *>(p));
+	} else if constexpr (Q == 4) {
+		st_x1<true>(p, v[0] | v[1] << 8 | v[2] << 16 | v[3] << 24);
+	} else {
+		__builtin_nontemporal_store((uint16_t)(v[0] | v[1] << 8), reinterpret_cast<uint16_t *>(p));
+	}
+}
+
+/* Local delivery (cgpu_deliver_v4 / _v6, include/cgpu.h): the destination
+ * endpoint's ingress policy for the packets a forwarding step marked
+ * CGPU_FWD_LOCAL -- ipv4_local_delivery / ipv6_local_delivery (lib/l3.h:71-132)
+ * store the label in CB_SRC_LABEL and tail-call cilium_policy[lxc_id], whose
+ * ipv4_policy / ipv6_policy (bpf_lxc.c:863-978, :1002-1030) run
+ * policy_can_access_ingress(label, dport, proto) on that endpoint's map, the
+ * conntrack lookup taken as CT_NEW.  The label is the caller's word per
+ * packet (src_label) or the sending endpoint's SECLABEL (src_ep): no ipcache
+ * is walked and ingress_src_identity / ingress_secctx_world are not read.
+ *
+ * A lane takes Q consecutive packets.  vec: every column is aligned for one
+ * load / store of its Q elements (launch_deliver), which every whole quad
+ * then uses; the n % Q tail and unaligned columns go element by element.
+ * Packets that are not LOCAL or that the protocol gate ends pass act = false
+ * to policy_q and so issue no gather, as do those whose `arg` names no policy
+ * map (> 0xFFFF or >= max_ep: a miss).  Counters as k_classify<.., CTR = 1>:
+ * hot slots packed in LDS (len < PK_MAX_LEN, at most 2^22 packets per
+ * workgroup: launch_deliver), everything else two global atomics on the
+ * delta buffer; metrics wave-reduced.  The stream's pk buffer and the cold
+ * log are not used: only some packets of a batch are LOCAL. */
+template <int Q, int NT> __global__ __launch_bounds__(NT) void k_deliver(cgpu_snapshot s, dlv_args a, uint32_t vec)
+{
+	extern __shared__ __attribute__((aligned(16))) uint64_t lctr[];
+	/* metrics {reason 0 / 133 / 137, ingress} */
+	uint64_t mcnt[3] = {0, 0, 0}, mbyt[3] = {0, 0, 0};
+	for (uint32_t k = threadIdx.x; k < s.hot_slots; k += NT)
+		lctr[k] = 0;
+	__syncthreads();
+
+	const uint32_t icmp = a.v6 ? 58u : 1u;
+	const uint64_t nq = (a.n + Q - 1) / Q;
+	const uint64_t stride = (uint64_t)gridDim.x * NT;
+	for (uint64_t q = (uint64_t)blockIdx.x * NT + threadIdx.x; q < nq; q += stride) {
+		const uint64_t i0 = q * Q;
+		const bool whole = vec && i0 + Q <= a.n;
+		uint32_t action[Q], arg[Q], lab[Q], dport[Q], proto[Q], fl[Q], len[Q];
+		if (whole) {
+			ld_colq<Q>(a.action + i0, action);
+			ld_colq<Q>(a.arg + i0, arg);
+			if (a.src_label)
+				ld_colq<Q>(a.src_label + i0, lab);
+			else
+				ld_colq<Q>(a.src_ep + i0, lab);
+			ld_colq<Q>(a.dport + i0, dport);
+			ld_colq<Q>(a.proto + i0, proto);
+			ld_colq<Q>(a.flags + i0, fl);
+			ld_colq<Q>(a.len + i0, len);
+		} else {
+#pragma unroll
+			for (int u = 0; u < Q; u++) {
+				const uint64_t i = i0 + u;
+				const bool in = i < a.n;
+				const uint64_t j = in ? i : 0u;
+				/* past the end: not LOCAL, and nothing of it is stored */
+				action[u] = in ? ntl(a.action + j) : (uint32_t)CGPU_FWD_NONE;
+				arg[u] = ntl(a.arg + j);
+				lab[u] = a.src_label ? ntl(a.src_label + j) : ntl(a.src_ep + j);
+				dport[u] = ntl(a.dport + j);
+				proto[u] = ntl(a.proto + j);
+				fl[u] = ntl(a.flags + j);
+				len[u] = ntl(a.len + j);
+			}
+		}
+		bool local[Q], gated[Q], act[Q], eg[Q], frag[Q];
+		uint32_t ep[Q];
+		decision d[Q];
+#pragma unroll
+		for (int u = 0; u < Q; u++) {
+			local[u] = action[u] == (uint32_t)CGPU_FWD_LOCAL;
+			/* ct_lookup{4,6} protocol gate: ICMP (v4: 1, v6: 58), TCP, UDP */
+			gated[u] = s.ct_proto_gate && proto[u] != icmp && proto[u] != 6u && proto[u] != 17u;
+			act[u] = local[u] && !gated[u] && arg[u] < a.max_ep;
+			eg[u] = false;
+			/* IPv6 passes is_fragment = false (bpf_lxc.c:1015) */
+			frag[u] = !a.v6 && (fl[u] & CGPU_F_FRAGMENT);
+			ep[u] = arg[u] & 0xFFFFu;
+		}
+		if (!a.src_label) {
+			/* SECLABEL of the sending endpoint (lxc_config.h), 0 without an entry;
+			 * the Q words gathered together, by the packets that get a label */
+			const uint32_t *lx = reinterpret_cast<const uint32_t *>(s.lxc);
+			uint32_t sec[Q];
+#pragma unroll
+			for (int u = 0; u < Q; u++)
+				sec[u] = (local[u] && !gated[u] && lab[u] < s.n_lxc) ? lx[8u * lab[u] + 7u] : 0u;
+#pragma unroll
+			for (int u = 0; u < Q; u++)
+				lab[u] = sec[u];
+		}
+#pragma unroll
+		for (int u = 0; u < Q; u++)
+			d[u].id = lab[u];
+		policy_q<Q>(s, act, eg, frag, dport, proto, ep, d);
+
+		uint32_t v[Q], id[Q], st[Q];
+#pragma unroll
+		for (int u = 0; u < Q; u++) {
+			if (!local[u]) {
+				v[u] = 0u;
+				id[u] = 0u;
+				st[u] = CGPU_STAGE_NOT_LOCAL;
+				continue;
+			}
+			int32_t vd;
+			if (gated[u]) {
+				vd = DROP_CT_UNKNOWN_PROTO;
+				id[u] = 0u;
+				st[u] = 4u;
+			} else {
+				/* (act false here: policy_q left the miss, DROP_POLICY / 0 / -1) */
+				vd = d[u].v;
+				id[u] = lab[u];
+				st[u] = d[u].st;
+				if (d[u].ctr >= 0) {
+					const uint32_t c = (uint32_t)d[u].ctr;
+					if (c < s.hot_slots && len[u] < PK_MAX_LEN) {
+						atomicAdd((unsigned long long *)&lctr[c],
+							  (1ull << PK_SHIFT) | (unsigned long long)len[u]);
+					} else {
+						atomicAdd((unsigned long long *)&a.delta[2u * c], 1ull);
+						atomicAdd((unsigned long long *)&a.delta[2u * c + 1u],
+							  (unsigned long long)len[u]);
+					}
+				}
+			}
+			v[u] = (uint32_t)vd;
+			/* a proxy redirect (v > 0) traces TRACE_TO_PROXY: no metrics */
+			const uint32_t idx = vd > 0 ? 3u : vd == 0 ? 0u : (vd == DROP_POLICY ? 1u : 2u);
+#pragma unroll
+			for (int k = 0; k < 3; k++) {
+				mcnt[k] += (idx == (uint32_t)k) ? 1u : 0u;
+				mbyt[k] += (idx == (uint32_t)k) ? len[u] : 0u;
+			}
+		}
+		if (whole) {
+			st_colq<Q>(a.verdict + i0, v);
+			if (a.identity)
+				st_colq<Q>(a.identity + i0, id);
+			if (a.stage)
+				st_colq<Q>(a.stage + i0, st);
+		} else {
+#pragma unroll
+			for (int u = 0; u < Q; u++) {
+				const uint64_t i = i0 + u;
+				if (i >= a.n)
+					continue;
+				__builtin_nontemporal_store((int32_t)v[u], a.verdict + i);
+				if (a.identity)
+					__builtin_nontemporal_store(id[u], a.identity + i);
+				if (a.stage)
+					__builtin_nontemporal_store((uint8_t)st[u], a.stage + i);
+			}
+		}
+	}
+
+	/* metrics: wave-reduce, one atomic per nonzero reason per wave */
+	uint64_t *met = a.delta + 2ull * s.n_ctr_slots;
+	const uint32_t reasons[3] = {0u, 133u, 137u};
+#pragma unroll
+	for (int k = 0; k < 3; k++) {
+		const uint64_t c = wave_sum(mcnt[k]);
+		const uint64_t b = wave_sum(mbyt[k]);
+		if ((threadIdx.x & 63) == 0 && c) {
+			const uint32_t key = (reasons[k] * 4u + 1u) * 2u; /* dir 1: ingress */
+			atomicAdd((unsigned long long *)&met[key], (unsigned long long)c);
+			atomicAdd((unsigned long long *)&met[key + 1], (unsigned long long)b);
+		}
+	}
+	__syncthreads();
+	for (uint32_t k = threadIdx.x; k < s.hot_slots; k += NT) {
+		const uint64_t x = lctr[k];
+		if (x) {
+			atomicAdd((unsigned long long *)&a.delta[2u * k], x >> PK_SHIFT);
+			atomicAdd((unsigned long long *)&a.delta[2u * k + 1u], x & PK_BYTES_MASK);
+		}
+	}
+}
+
 unsigned grid_for(uint64_t n)
 {
 	uint64_t blocks = (n + BLOCK - 1) / BLOCK;
@@ -4557,6 +4778,56 @@ hipError_t launch_forward(const cgpu_snapshot &s, const fwd_tables &f, const fwd
 			hipLaunchKernelGGL((k_forward<false, CGPU_FWD_NETDEV>), g, b, 0, st, f, a);
 		else
 			hipLaunchKernelGGL((k_forward<false, CGPU_FWD_LXC>), g, b, 0, st, f, a);
+	}
+	return hipGetLastError();
+}
+
+/* packets per lane of k_deliver (DESIGN.md §4 has what the compiler reported) */
+#define DLV_Q 4
+
+/* every column of `a` aligned for one load / store of its DLV_Q elements */
+static bool dlv_aligned(const dlv_args &a)
+{
+	const uintptr_t a4 = (uintptr_t)a.arg | (uintptr_t)a.src_label | (uintptr_t)a.len | (uintptr_t)a.verdict |
+			     (uintptr_t)a.identity;
+	const uintptr_t a2 = (uintptr_t)a.src_ep | (uintptr_t)a.dport;
+	const uintptr_t a1 = (uintptr_t)a.action | (uintptr_t)a.proto | (uintptr_t)a.flags | (uintptr_t)a.stage;
+	return !(a4 & (DLV_Q * 4 - 1)) && !(a2 & (DLV_Q * 2 - 1)) && !(a1 & (DLV_Q - 1));
+}
+
+/* as the k_classify<.., CTR = 1> launcher: 1024-thread workgroups, <= 2 per
+ * CU (LDS), and at most 2^22 packets per workgroup (packed-counter
+ * exactness: a workgroup makes at most 2^10 trips of 1024 lanes x DLV_Q);
+ * CGPU_SCHED_GLOBAL_CTR: no LDS counters */
+hipError_t launch_deliver(const cgpu_snapshot &s0, const dlv_args &x, hipStream_t st)
+{
+	constexpr int NT = 1024;
+	const cgpu_snapshot s = with_lds_hot(s0, (s0.schedule & CGPU_SCHED_GLOBAL_CTR) ? 0u : X4_LDS_BUDGET / 8u);
+	const size_t lds = (size_t)s.hot_slots * 8u;
+	const uint64_t cap = 2ull * 256ull;
+	const uint64_t per_launch = cap * (1ull << 22); /* a multiple of DLV_Q: the chunks keep the alignment */
+	for (uint64_t off = 0; off < x.n; off += per_launch) {
+		dlv_args c = x;
+		const uint64_t m = std::min<uint64_t>(x.n - off, per_launch);
+		c.n = m;
+		c.action += off;
+		c.arg += off;
+		if (c.src_label)
+			c.src_label += off;
+		if (c.src_ep)
+			c.src_ep += off;
+		c.dport += off;
+		c.proto += off;
+		c.flags += off;
+		c.len += off;
+		c.verdict += off;
+		if (c.identity)
+			c.identity += off;
+		if (c.stage)
+			c.stage += off;
+		const uint64_t lanes = (m + DLV_Q - 1) / DLV_Q;
+		const unsigned g = (unsigned)std::min<uint64_t>((lanes + NT - 1) / NT, cap);
+		hipLaunchKernelGGL((k_deliver<DLV_Q, NT>), dim3(g), dim3(NT), lds, st, s, c, dlv_aligned(c) ? 1u : 0u);
 	}
 	return hipGetLastError();
 }

@@ -111,6 +111,27 @@ struct fwd_args {
 
 hipError_t launch_forward(const cgpu_snapshot &s, const fwd_tables &f, const fwd_args &a, hipStream_t st);
 
+/* local delivery (cgpu_deliver_v4 / _v6): the columns of cgpu_dlv_in /
+ * cgpu_dlv_out (exactly one of src_label / src_ep), the context's delta
+ * buffer, and max_ep = min(max_endpoints, 0x10000): an `arg` at or above it
+ * names no policy map */
+struct dlv_args {
+	const uint8_t *action;
+	const uint32_t *arg, *src_label;
+	const uint16_t *src_ep, *dport;
+	const uint8_t *proto, *flags;
+	const uint32_t *len;
+	int32_t *verdict;
+	uint32_t *identity;
+	uint8_t *stage;
+	uint64_t *delta;
+	uint64_t n;
+	uint32_t max_ep;
+	int v6;
+};
+
+hipError_t launch_deliver(const cgpu_snapshot &s, const dlv_args &a, hipStream_t st);
+
 struct prefilter_args {
 	const uint32_t *saddr4, *daddr4;
 	const uint8_t *saddr16, *daddr16;

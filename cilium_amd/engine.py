@@ -25,8 +25,8 @@ import ipaddress
 import numpy as np
 
 from . import layouts as L
-from ._abi import (CgpuConfig, CgpuError, CtlbOut, FrameTuples, Frames, FwdIn, FwdOut, FwdParams, Lb4Out,
-                   Lb4Tuples, Rnat4Out, Rnat6Out, TuplesV4, TuplesV4Ct, TuplesV6Ct, TuplesV6, check, lib)
+from ._abi import (CgpuConfig, CgpuError, CtlbOut, DlvIn, DlvOut, FrameTuples, Frames, FwdIn, FwdOut, FwdParams,
+                   Lb4Out, Lb4Tuples, Rnat4Out, Rnat6Out, TuplesV4, TuplesV4Ct, TuplesV6Ct, TuplesV6, check, lib)
 
 CIDR_V4_DYN, CIDR_V4_FIX, CIDR_V6_DYN, CIDR_V6_FIX = 0, 1, 2, 3
 BPF_ANY, BPF_NOEXIST, BPF_EXIST = 0, 1, 2
@@ -543,17 +543,22 @@ class Engine:
         return out
 
     def classify_v4(self, t: dict, out: dict | None = None, stage: bool = True, stream=None,
-                    tunnel: bool = False, forward: dict | None = None):
+                    tunnel: bool = False, forward: dict | None = None, deliver: bool = False):
         """t: dict of CUDA tensors saddr/daddr (int32 view of network-order
         u32), dport (int16), proto/flags (uint8), len (int32), ep (int16).
         tunnel=True: out["tunnel"] too (_classify_tun).  forward=<dict of
         forward_v4's mode / encap / ipv4_mask / host_ifindex / encap_ifindex>:
         the tunnel form, then the forwarding step on its outputs into
         out["fwd_action"], ["fwd_ret"], ["fwd_ifindex"], ["fwd_arg"]
-        (_forward_into; t may hold "ttl")."""
+        (_forward_into; t may hold "ttl").  deliver=True (only with forward=
+        in FWD_LXC mode): then the destination endpoint's ingress policy for
+        the LOCAL packets, with t["ep"] as the sender, into out["dlv_verdict"],
+        ["dlv_identity"], ["dlv_stage"] (_deliver_into)."""
+        self._check_deliver(deliver, forward)
         if forward is not None:
             out = self._classify_tun(False, self.PATH_PLAIN, t, out, stage, stream)
-            return self._forward_into(False, t, out, forward, stream)
+            out = self._forward_into(False, t, out, forward, stream)
+            return self._deliver_into(False, t, out, stream) if deliver else out
         if tunnel:
             return self._classify_tun(False, self.PATH_PLAIN, t, out, stage, stream)
         import torch
@@ -654,7 +659,7 @@ class Engine:
 
     def classify_v4_ct(self, t: dict, now: int, out: dict | None = None, stage: bool = True,
                        stream=None, tunnel: bool = False, rev_nat: bool = False,
-                       forward: dict | None = None):
+                       forward: dict | None = None, deliver: bool = False):
         """Stateful classification (cgpu_classify_v4_ct): t holds CUDA tensors
         saddr/daddr (int32), sport/dport (int16, network order), proto/flags
         (uint8), l4b (int16: TCP header bytes 12-13 / ICMP type), len (int32),
@@ -662,7 +667,10 @@ class Engine:
         tunnel=True: out["tunnel"] too (_ct_tun).  rev_nat=True
         (cgpu_classify_v4_ct_rnat): out["rn_saddr"], ["rn_daddr"] (int32),
         ["rn_sport"] (int16), ["rn_applied"] (uint8), the frame after the
-        replies' reverse NAT.  forward=: as classify_v4, on the tunnel form."""
+        replies' reverse NAT.  forward=: as classify_v4, on the tunnel form;
+        deliver=True raises (the conntrack form of the delivery step is not
+        built)."""
+        self._no_deliver_ct(deliver, "classify_v4_ct")
         if (tunnel or forward is not None) and rev_nat:
             raise ValueError("tunnel / forward and rev_nat cannot be combined")
         if forward is not None:
@@ -744,10 +752,11 @@ class Engine:
 
     def classify_v6_ct(self, t: dict, now: int, out: dict | None = None, stage: bool = True,
                        stream=None, tunnel: bool = False, rev_nat: bool = False,
-                       forward: dict | None = None):
+                       forward: dict | None = None, deliver: bool = False):
         """cgpu_classify_v6_ct: as classify_v4_ct with saddr / daddr (n, 16)
         uint8 tensors (16-byte aligned rows).  rev_nat=True: out["rn_saddr"]
         (n, 16) uint8, ["rn_sport"], ["rn_applied"] (IPv6 has no rn_daddr)."""
+        self._no_deliver_ct(deliver, "classify_v6_ct")
         if (tunnel or forward is not None) and rev_nat:
             raise ValueError("tunnel / forward and rev_nat cannot be combined")
         if forward is not None:
@@ -864,12 +873,15 @@ class Engine:
         return out
 
     def classify_v6(self, t: dict, out: dict | None = None, stage: bool = True, stream=None,
-                    tunnel: bool = False, forward: dict | None = None):
+                    tunnel: bool = False, forward: dict | None = None, deliver: bool = False):
         """t: saddr/daddr uint8 CUDA tensors of shape (n, 16) (16-byte
-        aligned), the other columns as classify_v4 (forward= too)."""
+        aligned), the other columns as classify_v4 (forward= and deliver=
+        too)."""
+        self._check_deliver(deliver, forward)
         if forward is not None:
             out = self._classify_tun(True, self.PATH_PLAIN, t, out, stage, stream)
-            return self._forward_into(True, t, out, forward, stream)
+            out = self._forward_into(True, t, out, forward, stream)
+            return self._deliver_into(True, t, out, stream) if deliver else out
         if tunnel:
             return self._classify_tun(True, self.PATH_PLAIN, t, out, stage, stream)
         import torch
@@ -997,6 +1009,69 @@ class Engine:
         for k, v in f.items():
             out["fwd_" + k] = v
         return out
+
+    def _deliver(self, v6: bool, action, arg, dport, proto, flags, len, src_label, src_ep, out, stream):
+        import torch
+        if (src_label is None) == (src_ep is None):
+            raise ValueError("exactly one of src_label and src_ep is needed")
+        n = action.numel()
+        dev = action.device
+        if out is None:
+            out = {"verdict": torch.empty(n, dtype=torch.int32, device=dev),
+                   "identity": torch.empty(n, dtype=torch.int32, device=dev),
+                   "stage": torch.empty(n, dtype=torch.uint8, device=dev)}
+        iv = DlvIn(*[x.data_ptr() if x is not None else None
+                     for x in (action, arg, src_label, src_ep, dport, proto, flags, len)])
+        ov = DlvOut(*[out[k].data_ptr() if out.get(k) is not None else None
+                      for k in ("verdict", "identity", "stage")])
+        fn = "cgpu_deliver_v6" if v6 else "cgpu_deliver_v4"
+        check(getattr(self.L, fn)(self.h, C.byref(iv), n, C.byref(ov), _stream(stream)), fn)
+        return out
+
+    def deliver_v4(self, action, arg, dport, proto, flags, len, src_label=None, src_ep=None, out=None,
+                   stream=None):
+        """cgpu_deliver_v4: the destination endpoint's ingress policy for the
+        packets a forwarding step marked FWD_LOCAL (include/cgpu.h).  action
+        (uint8) and arg (int32 / uint32) are that step's outputs; dport
+        (int16), proto / flags (uint8) and len (int32) the classify call's
+        columns; the label per packet is src_label (int32 / uint32) or the
+        SECLABEL of the endpoint id src_ep (int16) -- exactly one of the two.
+        Returns {"verdict", "identity" (int32), "stage" (uint8)}; packets that
+        are not LOCAL read (0, 0, L.STAGE_NOT_LOCAL).  A given `out` may
+        leave identity and stage None."""
+        return self._deliver(False, action, arg, dport, proto, flags, len, src_label, src_ep, out, stream)
+
+    def deliver_v6(self, action, arg, dport, proto, flags, len, src_label=None, src_ep=None, out=None,
+                   stream=None):
+        """cgpu_deliver_v6: deliver_v4 for IPv6 packets (ICMPv6 passes the
+        protocol gate, the fragment bit is not read)."""
+        return self._deliver(True, action, arg, dport, proto, flags, len, src_label, src_ep, out, stream)
+
+    def _deliver_into(self, v6: bool, t: dict, out: dict, stream):
+        """deliver=True of a classify call: the delivery step on the call's
+        own fwd_action / fwd_arg and dport, proto, flags, len, with t["ep"] as
+        the sending endpoint, into out["dlv_*"]."""
+        if out.get("fwd_arg") is None:
+            raise ValueError("deliver=True needs the forwarding step's arg output (out['fwd_arg'])")
+        given = {k: out.get("dlv_" + k) for k in ("verdict", "identity", "stage")}
+        d = (self.deliver_v6 if v6 else self.deliver_v4)(
+            out["fwd_action"], out["fwd_arg"], t["dport"], t["proto"], t["flags"], t["len"], src_ep=t["ep"],
+            out=given if given["verdict"] is not None else None, stream=stream)
+        for k, v in d.items():
+            out["dlv_" + k] = v
+        return out
+
+    @staticmethod
+    def _check_deliver(deliver, forward):
+        if deliver and (forward is None or forward.get("mode", L.FWD_LXC) != L.FWD_LXC):
+            raise ValueError("deliver=True needs forward= in FWD_LXC mode: the delivery step runs on that "
+                             "step's LOCAL packets with the sending endpoint's label")
+
+    @staticmethod
+    def _no_deliver_ct(deliver, what: str):
+        if deliver:
+            raise ValueError(f"{what} has no deliver= form: the conntrack form of the delivery step "
+                             "(its CT_INGRESS lookups and creates) is not built")
 
     @staticmethod
     def _no_forward(forward, what: str):

@@ -75,6 +75,7 @@ XDP_DROP, XDP_PASS = 1, 2
 # DROP_SNAPLEN: the XDP program returns XDP_DROP and records no drop reason
 VERDICT_XDP_DROP = -4097
 STAGE_XDP_DROP = 8
+STAGE_NOT_LOCAL = 9  # cgpu_deliver_v4 / _v6: the packet's action is not FWD_LOCAL
 METRIC_INGRESS, METRIC_EGRESS = 1, 2
 # CT direction (bpf/lib/common.h:327-328); policy_key.egress = !dir
 CT_EGRESS, CT_INGRESS = 0, 1

@@ -1452,6 +1452,75 @@ int cgpu_forward_v6(cgpu_ctx *ctx, const cgpu_fwd_params *params, const cgpu_fwd
 int cgpu_forward_table_bytes(cgpu_ctx *ctx, uint64_t *out);
 
 /* ------------------------------------------------------------------ */
+/* local delivery: the destination endpoint's ingress policy           */
+/* ------------------------------------------------------------------ */
+/*
+ * The third call of the chain classify -> forward -> deliver.  A packet the
+ * forwarding step marks CGPU_FWD_LOCAL is not through yet:
+ * ipv4_local_delivery / ipv6_local_delivery (bpf/lib/l3.h:71-132) store
+ * skb->cb[CB_SRC_LABEL] = seclabel and tail-call cilium_policy[ep->lxc_id],
+ * the destination endpoint's handle_policy -> ipv4_policy / ipv6_policy
+ * (bpf_lxc.c:863-978, :1002-1030), which runs policy_can_access_ingress(
+ * src_label, dport, proto) (lib/policy.h:126-146) on that endpoint's policy
+ * map and can still drop the packet or send it to the ingress proxy.
+ *
+ * Per packet, against the snapshot the call pins:
+ *   1. action != CGPU_FWD_LOCAL: verdict 0, identity 0, stage
+ *      CGPU_STAGE_NOT_LOCAL; no counter and no metric is touched, and the
+ *      packet's other columns (arg included) are not interpreted.
+ *   2. The label is src_label[i], or with src_ep the sending endpoint's
+ *      cgpu_lxc_info.sec_label (SECLABEL; 0 for an endpoint without an entry).
+ *      It is used exactly as handed in, reserved values included: unlike the
+ *      ingress tuples of cgpu_classify_v4 / _v6 neither the ipcache nor
+ *      ingress_src_identity / ingress_secctx_world replaces it (the sender's
+ *      SECLABEL, bpf_lxc.c:592, :287; from the netdev or the overlay the
+ *      secctx, bpf_netdev.c:429, bpf_overlay.c:115).
+ *   3. With ct_proto_gate, a protocol outside ICMP (v4: 1, v6: 58), TCP and
+ *      UDP: DROP_CT_UNKNOWN_PROTO (-137), identity 0, stage 4.
+ *   4. The three probes of __policy_can_access on the policy map of endpoint
+ *      `arg`, direction ingress, identity = the label, is_fragment =
+ *      CGPU_F_FRAGMENT on IPv4 and false on IPv6: verdict, identity and stage
+ *      are those of an ingress tuple of cgpu_classify_v4 / _v6 with that
+ *      identity and ep (0, the raw be16 proxy port, or DROP_POLICY; stage
+ *      1 / 2 / 3 / 0).  An arg above 0xFFFF or >= max_endpoints is a miss.
+ *   5. Counters and metrics are that tuple's: the hit entry's packets / bytes
+ *      and the {REASON_FORWARDED | 133 | 137, ingress} metrics; nothing for a
+ *      proxy redirect.
+ *
+ * This is the stateless decision: ipv4_policy's conntrack lookup is taken as
+ * CT_NEW, as on every stateless path here.  Not modelled: skip_proxy
+ * (tc_index_skip_proxy); the ifindex of the proxy redirect;
+ * DROP_MISSED_TAIL_CALL (-140) for an lxc_id whose program is not loaded (the
+ * engine has a policy map for every id, and an empty one denies); and the
+ * conntrack form, whose CT_INGRESS lookups and creates belong in batch order
+ * in the one map.
+ */
+#define CGPU_STAGE_NOT_LOCAL 9
+
+typedef struct cgpu_dlv_in { /* device pointers */
+	const uint8_t *action;     /* cgpu_fwd_out.action */
+	const uint32_t *arg;       /* cgpu_fwd_out.arg: the lxc_id of a LOCAL packet */
+	const uint32_t *src_label; /* CB_SRC_LABEL per packet, or NULL ... */
+	const uint16_t *src_ep;    /* ... then the sending endpoint (the classify call's ep) */
+	const uint16_t *dport;     /* the classify call's policy port, network order */
+	const uint8_t *proto;
+	const uint8_t *flags;      /* CGPU_F_FRAGMENT is read (IPv4 only); CGPU_F_EGRESS is ignored */
+	const uint32_t *len;
+} cgpu_dlv_in;
+
+typedef struct cgpu_dlv_out { /* device pointers; identity and stage may be NULL */
+	int32_t *verdict;
+	uint32_t *identity;
+	uint8_t *stage;
+} cgpu_dlv_out;
+
+/* -EINVAL for a null struct, a null required column, both or neither of
+ * src_label / src_ep, or a misaligned 2- / 4-byte column (all judged before
+ * the context); -ENODEV on a host-only context; n == 0 returns 0. */
+int cgpu_deliver_v4(cgpu_ctx *ctx, const cgpu_dlv_in *in, size_t n, const cgpu_dlv_out *out, void *stream);
+int cgpu_deliver_v6(cgpu_ctx *ctx, const cgpu_dlv_in *in, size_t n, const cgpu_dlv_out *out, void *stream);
+
+/* ------------------------------------------------------------------ */
 /* counters                                                             */
 /* ------------------------------------------------------------------ */
 /*
