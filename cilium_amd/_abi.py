@@ -92,6 +92,17 @@ class FwdOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("action", "ret", "ifindex", "arg")]
 
 
+class FwdfParams(C.Structure):
+    _fields_ = [("fwd", FwdParams), ("host_mac", C.c_uint8 * 6), ("pad", C.c_uint8 * 2),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class FwdfIn(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("len", C.c_void_p), ("flags", C.c_void_p),
+                ("stride", C.c_uint32), ("reserved", C.c_uint32),
+                ("verdict", C.c_void_p), ("stage", C.c_void_p), ("tunnel", C.c_void_p)]
+
+
 class DlvIn(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("action", "arg", "src_label", "src_ep", "dport", "proto", "flags", "len")]
 
@@ -158,6 +169,7 @@ PROTOS = {
     "cgpu_forward_v4": (i32, [vp, C.POINTER(FwdParams), C.POINTER(FwdIn), sz, C.POINTER(FwdOut), vp]),
     "cgpu_forward_v6": (i32, [vp, C.POINTER(FwdParams), C.POINTER(FwdIn), sz, C.POINTER(FwdOut), vp]),
     "cgpu_forward_table_bytes": (i32, [vp, vp]),
+    "cgpu_forward_frames": (i32, [vp, C.POINTER(FwdfParams), C.POINTER(FwdfIn), sz, C.POINTER(FwdOut), vp]),
     "cgpu_deliver_v4": (i32, [vp, C.POINTER(DlvIn), sz, C.POINTER(DlvOut), vp]),
     "cgpu_deliver_v6": (i32, [vp, C.POINTER(DlvIn), sz, C.POINTER(DlvOut), vp]),
     "cgpu_lb4_update": (i32, [vp, vp, vp, u64]),

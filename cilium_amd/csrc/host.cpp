@@ -2081,6 +2081,7 @@ struct Epoch {
 	cgpu_snapshot snap{};
 	ipc_tun tun{}; /* into bufs[G_IPC]; t4.d16 == NULL without cgpu_config.ipcache_tunnel */
 	fwd_tables fwd{}; /* into fwdbuf; e4 == NULL: not built */
+	fwd_macs fwdm{};  /* into fwdbuf, with fwd */
 	DevBufP bufs[G_N];
 	DevBufP fwdbuf;   /* outside the verified groups: cgpu_table_bytes / _checksum / _verify leave it out */
 	hipEvent_t ready = nullptr;
@@ -4312,15 +4313,19 @@ static int commit_lxc(cgpu_ctx *c, CommitIn &in, cgpu_snapshot &s, DevBufP &buf)
 
 /* rows of W words into a single-slot neighbourhood hash (tables.h fwd_tables):
  * first fit within POL_HOP slots of the home slot, the table doubled until
- * every row fits; word T of a slot is FWD_USED | hop << 24 (0 in `rows`) */
+ * every row fits; word T of a slot is FWD_USED | hop << 24 (0 in `rows`);
+ * at (optional): the slot each row landed in */
 template <size_t W, size_t T, class H>
 static void build_hop(const std::vector<std::array<uint32_t, W>> &rows, H home_of,
-		      std::vector<std::array<uint32_t, W>> &out, uint32_t &mask)
+		      std::vector<std::array<uint32_t, W>> &out, uint32_t &mask,
+		      std::vector<uint32_t> *at = nullptr)
 {
 	uint32_t nb = next_pow2(std::max<uint64_t>(64, 2 * rows.size()));
 	for (;; nb *= 2) {
 		out.assign(nb, std::array<uint32_t, W>{});
 		mask = nb - 1;
+		if (at)
+			at->clear();
 		bool ok = true;
 		for (auto &r : rows) {
 			const uint32_t home = home_of(r) & mask;
@@ -4336,6 +4341,8 @@ static void build_hop(const std::vector<std::array<uint32_t, W>> &rows, H home_o
 			sl = r;
 			sl[T] = hop | FWD_USED;
 			out[home][T] |= 1u << (POL_HOP_SHIFT + d);
+			if (at)
+				at->push_back((home + d) & mask);
 		}
 		if (ok)
 			return;
@@ -4348,11 +4355,16 @@ static int commit_fwd(cgpu_ctx *c, CommitIn &in, Epoch &e)
 {
 	e.fwdbuf.reset();
 	e.fwd = fwd_tables{};
+	e.fwdm = fwd_macs{};
 	c->b.sum_fwd = 0;
 	if (in.fwd_ep.empty() && in.fwd_tun.empty())
 		return 0;
 	std::vector<std::array<uint32_t, 4>> r4, t4, o_e4, o_t4;
 	std::vector<std::array<uint32_t, 8>> r6, t6, o_e6, o_t6;
+	/* per row of r4 / r6: mac's and node_mac's first six bytes as stored, and
+	 * the slot the row lands in */
+	std::vector<std::array<uint8_t, 16>> mac4, mac6;
+	std::vector<uint32_t> at4, at6;
 	static const cgpu_endpoint_info zero{};
 	uint64_t sum = 0;
 	/* only keys the programs build can match (lookup_ip4_endpoint /
@@ -4370,10 +4382,16 @@ static int commit_fwd(cgpu_ctx *c, CommitIn &in, Epoch &e)
 		uint32_t w[4];
 		const uint32_t fam = words(kv.first, w);
 		const uint32_t val = (uint32_t)v.lxc_id | ((v.flags & CGPU_ENDPOINT_F_HOST) ? FWD_HOST_BIT : 0u);
-		if (fam == 1 && !w[1] && !w[2] && !w[3])
+		std::array<uint8_t, 16> m{};
+		memcpy(m.data(), &v.mac, 6);
+		memcpy(m.data() + 6, &v.node_mac, 6);
+		if (fam == 1 && !w[1] && !w[2] && !w[3]) {
 			r4.push_back({w[0], v.ifindex, val, 0});
-		else if (fam == 2)
+			mac4.push_back(m);
+		} else if (fam == 2) {
 			r6.push_back({w[0], w[1], w[2], w[3], v.ifindex, val, 0, 0});
+			mac6.push_back(m);
+		}
 	}
 	for (auto &kv : in.fwd_tun) {
 		sum += fnv(fnv(41, kv.first.data(), 20), kv.second.data(), 20);
@@ -4386,14 +4404,22 @@ static int commit_fwd(cgpu_ctx *c, CommitIn &in, Epoch &e)
 			t6.push_back({w[0], w[1], w[2], ip4, 0, 0, 0, 0});
 	}
 	fwd_tables f{};
-	build_hop<4, 3>(r4, [](const std::array<uint32_t, 4> &r) { return fwd_hash4(r[0]); }, o_e4, f.e4_mask);
+	build_hop<4, 3>(r4, [](const std::array<uint32_t, 4> &r) { return fwd_hash4(r[0]); }, o_e4, f.e4_mask, &at4);
 	build_hop<4, 3>(t4, [](const std::array<uint32_t, 4> &r) { return fwd_hash4(r[0]); }, o_t4, f.t4_mask);
 	build_hop<8, 6>(r6, [](const std::array<uint32_t, 8> &r) { return fold6(r[0], r[1], r[2], r[3]); }, o_e6,
-			f.e6_mask);
+			f.e6_mask, &at6);
 	build_hop<8, 6>(t6, [](const std::array<uint32_t, 8> &r) { return fold6(r[0], r[1], r[2], 0u); }, o_t6,
 			f.t6_mask);
+	/* the endpoints' MACs at the slot / row their key landed in (fwd_macs) */
+	std::vector<std::array<uint8_t, 16>> m4(o_e4.size(), std::array<uint8_t, 16>{}),
+		m6(o_e6.size(), std::array<uint8_t, 16>{});
+	for (size_t i = 0; i < r4.size(); i++)
+		m4[at4[i]] = mac4[i];
+	for (size_t i = 0; i < r6.size(); i++)
+		m6[at6[i]] = mac6[i];
 	Arena ar;
 	const size_t a_e4 = ar.add(o_e4.data(), o_e4.size() * 16), a_e6 = ar.add(o_e6.data(), o_e6.size() * 32);
+	const size_t a_m4 = ar.add(m4.data(), m4.size() * 16), a_m6 = ar.add(m6.data(), m6.size() * 16);
 	const size_t a_t4 = ar.add(o_t4.data(), o_t4.size() * 16), a_t6 = ar.add(o_t6.data(), o_t6.size() * 32);
 	if (int r = upload(c, ar, e.fwdbuf, G_N)) /* G_N: summed into the scratch word, not a verified group */
 		return r;
@@ -4402,6 +4428,7 @@ static int commit_fwd(cgpu_ctx *c, CommitIn &in, Epoch &e)
 	f.t4 = at<uint4>(e.fwdbuf, a_t4);
 	f.t6 = at<uint4>(e.fwdbuf, a_t6);
 	e.fwd = f;
+	e.fwdm = fwd_macs{at<uint4>(e.fwdbuf, a_m4), at<uint4>(e.fwdbuf, a_m6)};
 	c->b.sum_fwd = sum;
 	return 0;
 }
@@ -4479,6 +4506,7 @@ static int commit_locked(cgpu_ctx *c, uint64_t *epoch_out)
 		e->snap = prev->snap;
 		e->tun = prev->tun;
 		e->fwd = prev->fwd;
+		e->fwdm = prev->fwdm;
 		e->fwdbuf = prev->fwdbuf;
 		for (int k = 0; k < G_N; k++)
 			e->bufs[k] = prev->bufs[k];
@@ -5422,6 +5450,62 @@ CGPU_EXPORT int cgpu_forward_v6(cgpu_ctx *c, const cgpu_fwd_params *p, const cgp
 				const cgpu_fwd_out *out, void *stream)
 {
 	return forward_batch(c, p, in, n, out, 1, stream);
+}
+
+/* the forwarding step on raw frames (cgpu.h cgpu_forward_frames): the whole
+ * call is judged before the context */
+CGPU_EXPORT int cgpu_forward_frames(cgpu_ctx *c, const cgpu_fwdf_params *p, const cgpu_fwdf_in *in, size_t n,
+				    const cgpu_fwd_out *out, void *stream)
+{
+	if (!c || !p || !in || !out)
+		return fail(-EINVAL, "null argument");
+	const cgpu_fwd_params &fp = p->fwd;
+	if (fp.mode != CGPU_FWD_LXC && fp.mode != CGPU_FWD_NETDEV)
+		return fail(-EINVAL, "bad forwarding mode %u", fp.mode);
+	if ((fp.flags & ~CGPU_FWD_ENCAP) || (p->flags & ~CGPU_FWDF_REWRITE))
+		return fail(-EINVAL, "unknown forwarding flags 0x%x / 0x%x", fp.flags, p->flags);
+	if (fp.reserved[0] || fp.reserved[1] || fp.reserved[2] || p->reserved[0] || p->reserved[1] || p->reserved[2] ||
+	    p->pad[0] || p->pad[1] || in->reserved)
+		return fail(-EINVAL, "cgpu_fwdf_params / cgpu_fwdf_in reserved and pad must be 0");
+	if (in->stride < 64 || (in->stride & 15))
+		return fail(-EINVAL, "frame stride must be a multiple of 16 and >= 64");
+	if ((uintptr_t)in->data & 15)
+		return fail(-EINVAL, "frame buffer must be 16-byte aligned");
+	if (n && (!in->data || !in->len || !out->action))
+		return fail(-EINVAL, "null data, len or action column");
+	if (n && fp.mode == CGPU_FWD_LXC && (!in->verdict || !in->flags || !in->stage))
+		return fail(-EINVAL, "CGPU_FWD_LXC needs the verdict, stage and flags columns");
+	if (((uintptr_t)in->len | (uintptr_t)in->verdict | (uintptr_t)in->tunnel | (uintptr_t)out->ret |
+	     (uintptr_t)out->ifindex | (uintptr_t)out->arg) & 3u)
+		return fail(-EINVAL, "4-byte column not 4-byte aligned");
+	Pinned P;
+	if (int r = pin(c, stream, P))
+		return r;
+	if (!n)
+		return 0;
+	fwdf_args a{};
+	a.data = in->data;
+	a.len = in->len;
+	a.flags = in->flags;
+	a.stage = in->stage;
+	a.verdict = in->verdict;
+	a.tunnel = in->tunnel;
+	a.action = out->action;
+	a.ret = out->ret;
+	a.ifindex = out->ifindex;
+	a.arg = out->arg;
+	a.n = n;
+	a.stride = in->stride;
+	a.mode = fp.mode;
+	a.encap = fp.flags & CGPU_FWD_ENCAP;
+	a.rewrite = p->flags & CGPU_FWDF_REWRITE;
+	a.ipv4_mask = fp.ipv4_mask;
+	a.host_ifindex = fp.host_ifindex;
+	a.encap_ifindex = fp.encap_ifindex;
+	memcpy(&a.host_mac_lo, p->host_mac, 4);
+	a.host_mac_hi = (uint32_t)p->host_mac[4] | ((uint32_t)p->host_mac[5] << 8);
+	HIP_OR_EIO(launch_forward_frames(P.snap(), P.ep->fwd, P.ep->fwdm, a, (hipStream_t)stream));
+	return 0;
 }
 
 /* local delivery (cgpu.h cgpu_deliver_v4 / _v6): the call's shape is judged

@@ -3373,7 +3373,7 @@ __global__ __launch_bounds__(NT) void k_frames(cgpu_snapshot s, frames_args a)
 			}
 		} else if (t.status == FRAME_NOT_CLASSIFIED) {
 			v = 0;
-			st = 7;
+			st = CGPU_STAGE_NOT_CLASSIFIED;
 		} else {
 			v = t.status;
 			st = v == DROP_CT_UNKNOWN_PROTO ? 4u : 5u;
@@ -3384,7 +3384,7 @@ __global__ __launch_bounds__(NT) void k_frames(cgpu_snapshot s, frames_args a)
 			a.stage[i] = (uint8_t)st;
 		/* not classified, snap-length, or a proxy redirect (TRACE_TO_PROXY
 		 * counts nothing): no metrics */
-		if (st == 7u || v == DROP_SNAPLEN || v > 0)
+		if (st == CGPU_STAGE_NOT_CLASSIFIED || v == DROP_SNAPLEN || v > 0)
 			continue;
 		/* update_metrics(len, dir, -reason) (bpf/lib/drop.h:104), reason as u8 */
 		const uint32_t reason = v < 0 ? (uint32_t)(-v) & 0xffu : 0u;
@@ -4037,6 +4037,235 @@ __global__ __launch_bounds__(BLOCK) void k_forward(fwd_tables F, fwd_args a)
 			__builtin_nontemporal_store(ifx, a.ifindex + i);
 		if (a.arg)
 			__builtin_nontemporal_store(arg, a.arg + i);
+	}
+}
+
+/* fwd_find4 / fwd_find6<4> returning the slot / row index of the hit as well
+ * (the endpoints' MACs sit at that index of fwd_macs); ~0u: no hit.  A copy
+ * of the two walks and not a helper under them: with fwd_find4 / fwd_find6 as
+ * wrappers around these, k_forward compiled to more registers (IPv4 30 -> 31
+ * and 28 -> 29 VGPRs, IPv6 28 -> 36 and 26 -> 34), and that kernel stays as
+ * it is.  A change of the hop walk goes into both. */
+__device__ __forceinline__ uint32_t fwd_slot4(const uint4 *t, uint32_t mask, uint32_t home, uint32_t key, uint4 q,
+					      uint4 &hit)
+{
+	uint32_t hop = q.w >> POL_HOP_SHIFT;
+	while (hop) {
+		const uint32_t j = (uint32_t)__ffs((int)hop) - 1u;
+		hop &= hop - 1u;
+		if (j)
+			q = t[(home + j) & mask];
+		if (q.x == key) {
+			hit = q;
+			return (home + j) & mask;
+		}
+	}
+	return ~0u;
+}
+
+__device__ __forceinline__ uint32_t fwd_slot6(const uint4 *t, uint32_t mask, uint32_t home, uint4 key, uint4 q0,
+					      uint4 q1, uint4 &h1)
+{
+	uint32_t hop = q1.z >> POL_HOP_SHIFT;
+	while (hop) {
+		const uint32_t j = (uint32_t)__ffs((int)hop) - 1u;
+		hop &= hop - 1u;
+		if (j) {
+			const uint4 *r = t + 2u * (size_t)((home + j) & mask);
+			q0 = r[0];
+			q1 = r[1];
+		}
+		if (q0.x == key.x && q0.y == key.y && q0.z == key.z && q0.w == key.w) {
+			h1 = q1;
+			return (home + j) & mask;
+		}
+	}
+	return ~0u;
+}
+
+/* bpf_l3_csum_replace(.., from = ttl, to = ttl - 1, 2) on the checksum field
+ * c as loaded (cgpu.h cgpu_forward_frames has the arithmetic): csum_add is
+ * the kernel's 32-bit end-around-carry add */
+__device__ __forceinline__ uint32_t csum_add32(uint32_t a, uint32_t b)
+{
+	const uint32_t r = a + b;
+	return r + (r < b ? 1u : 0u);
+}
+
+__device__ __forceinline__ uint32_t csum_dec_ttl(uint32_t c, uint32_t ttl)
+{
+	uint32_t t = csum_add32(csum_add32(~c, ~ttl), ttl - 1u);
+	t = (t & 0xFFFFu) + (t >> 16);
+	t = (t & 0xFFFFu) + (t >> 16);
+	return ~t & 0xFFFFu;
+}
+
+/* The forwarding step on raw frames (cgpu_forward_frames; cgpu.h has the
+ * rules): k_forward's decision, restated for a family read per frame from
+ * the frame itself, and with RW the branch's L2 / L3 rewrite in the slot.
+ * One frame per lane in batch order, grid-stride; the slot's first 64 bytes
+ * are loaded as parse_frame loads them.  The endpoint's home slot and, in the
+ * ENCAP build, the tunnel map's are gathered by every lane before anything is
+ * decided (a frame that is not IP gathers slot 0 and drops it); an IPv4 lane
+ * loads its 16-B slot twice where an IPv6 lane loads the two halves of its
+ * row, so that the gathers stay outside any per-lane branch.  Only a LOCAL
+ * lane of an RW launch reads the MACs, at the slot its key was found in.
+ * Every byte the rewrite changes lies in the slot's first 32: a rewriting
+ * lane stores those two 16-B words, any other lane stores nothing. */
+template <int MODE, bool RW>
+__global__ __launch_bounds__(BLOCK) void k_forward_frames(fwd_tables F, fwd_macs M, fwdf_args a)
+{
+	const uint64_t stride = (uint64_t)gridDim.x * BLOCK;
+	const bool built = F.e4 != nullptr;
+	const bool encap = a.encap != 0u;
+	for (uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i < a.n; i += stride) {
+		uint8_t *f = a.data + i * (uint64_t)a.stride;
+		uint4 w0 = ld_x4<true>(f), w1 = ld_x4<true>(f + 16);
+		const uint4 w2 = ld_x4<true>(f + 32), w3 = ld_x4<true>(f + 48);
+		const uint32_t cap = min(ntl(a.len + i), a.stride);
+		const int32_t verdict = MODE == CGPU_FWD_LXC ? (int32_t)ntl(a.verdict + i) : 0;
+		const bool egress = MODE == CGPU_FWD_LXC ? (ntl(a.flags + i) & CGPU_F_EGRESS) != 0u : true;
+		const bool responder = MODE == CGPU_FWD_LXC ? ntl(a.stage + i) == CGPU_STAGE_NOT_CLASSIFIED : false;
+		const uint32_t tun = a.tunnel ? ntl(a.tunnel + i) : 0u;
+
+		const uint32_t et = w0.w & 0xFFFFu; /* bytes 12..13 as loaded */
+		const bool v4 = et == 0x0008u && cap >= 34u;
+		const bool v6 = et == 0xDD86u && cap >= 54u;
+		uint4 da = make_uint4(0, 0, 0, 0);
+		uint32_t ttl;
+		if (v6) {
+			da.x = (w2.y >> 16) | (w2.z << 16);
+			da.y = (w2.z >> 16) | (w2.w << 16);
+			da.z = (w2.w >> 16) | (w3.x << 16);
+			da.w = (w3.x >> 16) | (w3.y << 16);
+			ttl = (w1.y >> 8) & 0xFFu;
+		} else {
+			da.x = (w1.w >> 16) | (w2.x << 16);
+			ttl = (w1.y >> 16) & 0xFFu;
+		}
+		const bool expired = ttl <= 1u;
+
+		bool ep_hit = false, tm_hit = false;
+		uint32_t ep_if = 0, ep_w = 0, tm_ip = 0, ep_at = 0;
+		if (built) {
+			const uint32_t tk = da.x & a.ipv4_mask;
+			const uint32_t he = v6 ? fold6(da.x, da.y, da.z, da.w) & F.e6_mask
+					       : (v4 ? fwd_hash4(da.x) & F.e4_mask : 0u);
+			const uint32_t ht = v6 ? fold6(da.x, da.y, da.z, 0u) & F.t6_mask
+					       : (v4 ? fwd_hash4(tk) & F.t4_mask : 0u);
+			const uint4 *re = v6 ? F.e6 + 2u * (size_t)he : F.e4 + he;
+			const uint4 *rt = v6 ? F.t6 + 2u * (size_t)ht : F.t4 + ht;
+			const uint4 e0 = re[0], e1 = re[v6 ? 1 : 0];
+			uint4 t0 = make_uint4(0, 0, 0, 0), t1 = t0, h0, h1;
+			if (encap) {
+				t0 = rt[0];
+				t1 = rt[v6 ? 1 : 0];
+			}
+			if (v6) {
+				ep_at = fwd_slot6(F.e6, F.e6_mask, he, da, e0, e1, h1);
+				if (ep_at != ~0u) {
+					ep_hit = true;
+					ep_if = h1.x;
+					ep_w = h1.y;
+				}
+				if (encap && fwd_find6<3>(F.t6, F.t6_mask, ht, da, t0, t1, h0, h1)) {
+					tm_hit = true;
+					tm_ip = h0.w;
+				}
+			} else if (v4) {
+				ep_at = fwd_slot4(F.e4, F.e4_mask, he, da.x, e0, h0);
+				if (ep_at != ~0u) {
+					ep_hit = true;
+					ep_if = h0.y;
+					ep_w = h0.z;
+				}
+				if (encap && fwd_find4(F.t4, F.t4_mask, ht, tk, t0, h0)) {
+					tm_hit = true;
+					tm_ip = h0.y;
+				}
+			}
+		} else if (v6) {
+			const uint32_t b = pfx6_hash(da.x, da.y, da.z, da.w, 0u) & a.ep6.bucket_mask;
+			const uint4 *p = reinterpret_cast<const uint4 *>(a.ep6.slots) + (size_t)b * 4u;
+			ep_hit = set16_has_first(a.ep6, p[0], p[1].x, p[2], p[3].x, b, da);
+		} else if (v4) {
+			ep_hit = set4_has(a.ep4, da.x);
+		}
+
+		const bool gate = MODE == CGPU_FWD_LXC
+					  ? true
+					  : (v6 ? da.x == a.router[0] && da.y == a.router[1] && da.z == a.router[2]
+						: (da.x & a.cluster_mask) == a.cluster_range);
+		const bool host = (ep_w & FWD_HOST_BIT) != 0u;
+		uint32_t act, ifx = 0, arg = 0;
+		int32_t ret = 0;
+		bool l3 = false; /* the branch runs ipv4_l3 / ipv6_l3 */
+		if (!(v4 || v6) || responder || (MODE == CGPU_FWD_LXC && !egress)) {
+			act = CGPU_FWD_NONE;
+		} else if (MODE == CGPU_FWD_LXC && verdict < 0) {
+			act = CGPU_FWD_DROP;
+			ret = verdict;
+		} else if (MODE == CGPU_FWD_LXC && verdict > 0) {
+			act = CGPU_FWD_PROXY;
+			arg = (uint32_t)verdict;
+			ifx = a.host_ifindex;
+			l3 = true;
+		} else if (ep_hit && host) {
+			act = MODE == CGPU_FWD_LXC ? CGPU_FWD_HOST : CGPU_FWD_STACK;
+			ifx = MODE == CGPU_FWD_LXC ? a.host_ifindex : 0u;
+			l3 = MODE == CGPU_FWD_LXC;
+		} else if (ep_hit) {
+			act = CGPU_FWD_LOCAL;
+			ifx = ep_if;
+			arg = ep_w & 0xFFFFu;
+			l3 = true;
+		} else if (encap && (tun != 0u || (gate && tm_hit))) {
+			act = CGPU_FWD_OVERLAY;
+			arg = tun != 0u ? tun : tm_ip;
+			ifx = a.encap_ifindex;
+		} else {
+			act = CGPU_FWD_STACK;
+			l3 = MODE == CGPU_FWD_LXC;
+		}
+		if (l3 && expired) {
+			act = v6 ? CGPU_FWD_TIME_EXCEEDED : CGPU_FWD_DROP;
+			ret = v6 ? 0 : CGPU_DROP_INVALID;
+			ifx = arg = 0u;
+			l3 = false;
+		}
+		__builtin_nontemporal_store((uint8_t)act, a.action + i);
+		if (a.ret)
+			__builtin_nontemporal_store(ret, a.ret + i);
+		if (a.ifindex)
+			__builtin_nontemporal_store(ifx, a.ifindex + i);
+		if (a.arg)
+			__builtin_nontemporal_store(arg, a.arg + i);
+
+		if (RW && l3) { /* ipv4_l3 / ipv6_l3: PROXY, HOST, LOCAL, the egress STACK */
+			if (act == CGPU_FWD_LOCAL) { /* smac = ep->node_mac, dmac = ep->mac */
+				uint4 m = make_uint4(0, 0, 0, 0);
+				if (built)
+					m = v6 ? M.m6[ep_at] : M.m4[ep_at];
+				w0.x = m.x;
+				w0.y = m.y;
+				w0.z = m.z;
+			} else if (act == CGPU_FWD_STACK) { /* smac NULL, dmac = NODE_MAC */
+				w0.x = a.node_mac_lo;
+				w0.y = (w0.y & 0xFFFF0000u) | a.node_mac_hi;
+			} else { /* smac = NODE_MAC, dmac = HOST_IFINDEX_MAC */
+				w0.x = a.host_mac_lo;
+				w0.y = a.host_mac_hi | (a.node_mac_lo << 16);
+				w0.z = (a.node_mac_lo >> 16) | (a.node_mac_hi << 16);
+			}
+			if (v6) {
+				w1.y = (w1.y & ~0xFF00u) | ((ttl - 1u) << 8);
+			} else {
+				w1.y = (w1.y & ~0xFF0000u) | ((ttl - 1u) << 16);
+				w1.z = (w1.z & 0xFFFF0000u) | csum_dec_ttl(w1.z & 0xFFFFu, ttl);
+			}
+			st_x4<false>(f, w0.x, w0.y, w0.z, w0.w);
+			st_x4<false>(f + 16, w1.x, w1.y, w1.z, w1.w);
+		}
 	}
 }
 
@@ -4778,6 +5007,36 @@ hipError_t launch_forward(const cgpu_snapshot &s, const fwd_tables &f, const fwd
 			hipLaunchKernelGGL((k_forward<false, CGPU_FWD_NETDEV>), g, b, 0, st, f, a);
 		else
 			hipLaunchKernelGGL((k_forward<false, CGPU_FWD_LXC>), g, b, 0, st, f, a);
+	}
+	return hipGetLastError();
+}
+
+hipError_t launch_forward_frames(const cgpu_snapshot &s, const fwd_tables &f, const fwd_macs &m,
+				 const fwdf_args &x, hipStream_t st)
+{
+	if (!x.n)
+		return hipSuccess;
+	fwdf_args a = x;
+	a.ep4 = s.ep4;
+	a.ep6 = s.ep6;
+	a.cluster_mask = s.ipv4_cluster_mask;
+	a.cluster_range = s.ipv4_cluster_range;
+	a.router[0] = s.router_ip[0];
+	a.router[1] = s.router_ip[1];
+	a.router[2] = s.router_ip[2];
+	a.node_mac_lo = s.node_mac_lo;
+	a.node_mac_hi = s.node_mac_hi;
+	const dim3 g(grid_for(a.n)), b(BLOCK);
+	if (a.mode == CGPU_FWD_NETDEV) {
+		if (a.rewrite)
+			hipLaunchKernelGGL((k_forward_frames<CGPU_FWD_NETDEV, true>), g, b, 0, st, f, m, a);
+		else
+			hipLaunchKernelGGL((k_forward_frames<CGPU_FWD_NETDEV, false>), g, b, 0, st, f, m, a);
+	} else {
+		if (a.rewrite)
+			hipLaunchKernelGGL((k_forward_frames<CGPU_FWD_LXC, true>), g, b, 0, st, f, m, a);
+		else
+			hipLaunchKernelGGL((k_forward_frames<CGPU_FWD_LXC, false>), g, b, 0, st, f, m, a);
 	}
 	return hipGetLastError();
 }

@@ -111,6 +111,30 @@ struct fwd_args {
 
 hipError_t launch_forward(const cgpu_snapshot &s, const fwd_tables &f, const fwd_args &a, hipStream_t st);
 
+/* the forwarding step on raw frames (cgpu_forward_frames): the columns of
+ * cgpu_fwdf_in / cgpu_fwd_out, the words of cgpu_fwdf_params (host_mac as the
+ * little-endian words of its bytes 0-3 / 4-5); the snapshot's parts (as
+ * fwd_args, and NODE_MAC) are filled in by launch_forward_frames */
+struct fwdf_args {
+	uint8_t *data;
+	const uint32_t *len;
+	const uint8_t *flags, *stage;
+	const int32_t *verdict;
+	const uint32_t *tunnel;
+	uint8_t *action;
+	int32_t *ret;
+	uint32_t *ifindex, *arg;
+	uint64_t n;
+	uint32_t stride, mode, encap, rewrite, ipv4_mask, host_ifindex, encap_ifindex;
+	uint32_t host_mac_lo, host_mac_hi, node_mac_lo, node_mac_hi;
+	addr_set4 ep4;
+	addr_set16 ep6;
+	uint32_t cluster_mask, cluster_range, router[3];
+};
+
+hipError_t launch_forward_frames(const cgpu_snapshot &s, const fwd_tables &f, const fwd_macs &m,
+				 const fwdf_args &a, hipStream_t st);
+
 /* local delivery (cgpu_deliver_v4 / _v6): the columns of cgpu_dlv_in /
  * cgpu_dlv_out (exactly one of src_label / src_ep), the context's delta
  * buffer, and max_ep = min(max_endpoints, 0x10000): an `arg` at or above it

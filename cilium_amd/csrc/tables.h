@@ -537,6 +537,17 @@ typedef struct fwd_tables {
 	uint32_t e4_mask, e6_mask, t4_mask, t6_mask;
 } fwd_tables;
 
+/* The endpoints' MACs for the frame rewrite (cgpu_forward_frames): one 16-B
+ * word per slot of e4 / row of e6, same index: bytes 0..5 endpoint_info.mac's
+ * first six bytes as stored, 6..11 node_mac's, 12..15 zero -- a LOCAL frame's
+ * bytes 0..11 (dmac, smac).  Built and freed with the forwarding tables and
+ * handed to that call's kernel alone (fwd_tables and the kernarg of every
+ * other kernel stay as they are); m4 == NULL with e4 == NULL. */
+typedef struct fwd_macs {
+	const uint4 *m4; /* e4_mask + 1 */
+	const uint4 *m6; /* e6_mask + 1 */
+} fwd_macs;
+
 static inline __host__ __device__ uint32_t fwd_hash4(uint32_t a)
 {
 	return mix32(a, 0x46574434u);

@@ -26,7 +26,8 @@ import numpy as np
 
 from . import layouts as L
 from ._abi import (CgpuConfig, CgpuError, CtlbOut, DlvIn, DlvOut, FrameTuples, Frames, FwdIn, FwdOut, FwdParams,
-                   Lb4Out, Lb4Tuples, Rnat4Out, Rnat6Out, TuplesV4, TuplesV4Ct, TuplesV6Ct, TuplesV6, check, lib)
+                   FwdfIn, FwdfParams, Lb4Out, Lb4Tuples, Rnat4Out, Rnat6Out, TuplesV4, TuplesV4Ct, TuplesV6Ct,
+                   TuplesV6, check, lib)
 
 CIDR_V4_DYN, CIDR_V4_FIX, CIDR_V6_DYN, CIDR_V6_FIX = 0, 1, 2, 3
 BPF_ANY, BPF_NOEXIST, BPF_EXIST = 0, 1, 2
@@ -1138,11 +1139,25 @@ class Engine:
               "cgpu_frames_parse")
         return out
 
-    def classify_frames(self, f: dict, out: dict | None = None, stage: bool = True, stream=None):
-        """Raw frames to verdicts in one pass (cgpu_classify_frames)."""
+    _FWDF_KEYS = _FWD_KEYS + ("host_mac", "rewrite")
+
+    def classify_frames(self, f: dict, out: dict | None = None, stage: bool = True, stream=None,
+                        forward: dict | None = None):
+        """Raw frames to verdicts in one pass (cgpu_classify_frames).
+        forward=<forward_frames' keyword parameters mode, encap, ipv4_mask,
+        host_ifindex, encap_ifindex, host_mac, rewrite>: then the forwarding
+        step on the frames with the call's own verdict and stage and no
+        tunnel column, into out["fwd_action" / "fwd_ret" / "fwd_ifindex" /
+        "fwd_arg"]; with rewrite (the default) f["data"] is modified in place."""
         import torch
         n = f["len"].numel()
         dev = f["len"].device
+        if forward is not None:
+            bad = set(forward) - set(self._FWDF_KEYS)
+            if bad:
+                raise TypeError(f"unknown forward parameter(s) {sorted(bad)}")
+            if not stage and forward.get("mode", L.FWD_LXC) == L.FWD_LXC:
+                raise ValueError("forward= in FWD_LXC mode reads the stage output")
         if out is None:
             out = {"verdict": torch.empty(n, dtype=torch.int32, device=dev),
                    "identity": torch.empty(n, dtype=torch.int32, device=dev),
@@ -1151,6 +1166,47 @@ class Engine:
         check(self.L.cgpu_classify_frames(self.h, C.byref(fr), n, _ptr(out["verdict"]),
                                           _ptr(out["identity"]), _ptr(out.get("stage")),
                                           _stream(stream)), "cgpu_classify_frames")
+        if forward is not None:
+            given = {k: out.get("fwd_" + k) for k in ("action", "ret", "ifindex", "arg")}
+            r = self.forward_frames(f, verdict=out["verdict"], stage=out.get("stage"),
+                                    out=given if given["action"] is not None else None, stream=stream, **forward)
+            for k, v in r.items():
+                out["fwd_" + k] = v
+        return out
+
+    def forward_frames(self, f: dict, verdict=None, stage=None, tunnel=None, mode=L.FWD_LXC, encap=True,
+                       ipv4_mask=0xffff, host_ifindex=1, encap_ifindex=1, host_mac=bytes(6), rewrite=True,
+                       out=None, stream=None):
+        """cgpu_forward_frames: the decision of forward_v4 / _v6 per frame of
+        a mixed batch, on the frame's own daddr and ttl / hop limit, and with
+        `rewrite` that branch's MAC, ttl / hop limit and IPv4 checksum rewrite
+        in f["data"] itself (include/cgpu.h has the table).  f: the dict of
+        synth.frames_to_device (data (n, stride) uint8, len, flags; ep is not
+        read); verdict (int32) and stage (uint8) are classify_frames' outputs
+        (FWD_NETDEV reads neither, nor flags); tunnel: the raw tunnel_endpoint
+        words (None = all 0); host_mac: six bytes, the dmac of PROXY / HOST
+        frames.  Returns {"action", "ret", "ifindex", "arg"} as forward_v4."""
+        import torch
+        data = f["data"]
+        assert data.dim() == 2 and data.is_contiguous()
+        n = f["len"].numel()
+        dev = data.device
+        if out is None:
+            out = {"action": torch.empty(n, dtype=torch.uint8, device=dev),
+                   "ret": torch.empty(n, dtype=torch.int32, device=dev),
+                   "ifindex": torch.empty(n, dtype=torch.int32, device=dev),
+                   "arg": torch.empty(n, dtype=torch.int32, device=dev)}
+        host_mac = bytes(host_mac)
+        if len(host_mac) != 6:
+            raise ValueError("host_mac is six bytes")
+        p = FwdfParams(FwdParams(mode, L.FWD_ENCAP if encap else 0, ipv4_mask, host_ifindex, encap_ifindex),
+                       (C.c_uint8 * 6)(*host_mac), (C.c_uint8 * 2)(), L.FWDF_REWRITE if rewrite else 0)
+        iv = FwdfIn(data.data_ptr(), f["len"].data_ptr(), _ptr(f.get("flags")), data.shape[1], 0,
+                    _ptr(verdict), _ptr(stage), _ptr(tunnel))
+        ov = FwdOut(*[out[k].data_ptr() if out.get(k) is not None else None
+                      for k in ("action", "ret", "ifindex", "arg")])
+        check(self.L.cgpu_forward_frames(self.h, C.byref(p), C.byref(iv), n, C.byref(ov), _stream(stream)),
+              "cgpu_forward_frames")
         return out
 
     def classify_frames_host(self, f: dict, out: dict | None = None, stage: bool = True, stream=None):

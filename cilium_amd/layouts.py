@@ -252,6 +252,7 @@ ENDPOINT_F_HOST = 1
 # the forwarding step (include/cgpu.h cgpu_forward_v4 / _v6)
 FWD_LXC, FWD_NETDEV = 0, 1
 FWD_ENCAP = 1
+FWDF_REWRITE = 1  # cgpu_forward_frames: rewrite MACs, ttl / hop limit and IPv4 checksum in place
 FWD_NONE, FWD_DROP, FWD_PROXY, FWD_LOCAL, FWD_HOST, FWD_OVERLAY, FWD_STACK, FWD_TIME_EXCEEDED = range(8)
 DROP_INVALID = -134
 TUNNEL_ENDPOINT_MAP_SIZE = 65536  # bpf/node_config.h:54

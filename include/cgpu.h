@@ -826,6 +826,7 @@ typedef struct cgpu_frames {
 				       ICMPv6 responders take (bpf_lxc.c:377-386) or
 				       ingress non-IP (passed to the stack,
 				       bpf_netdev.c:518-520) */
+#define CGPU_STAGE_NOT_CLASSIFIED 7 /* the stage cgpu_classify_frames gives such a frame */
 #define CGPU_DROP_SNAPLEN (-4096)   /* a header the reference would read lies past
 				       the stored slot (stride < len): re-submit
 				       with a larger stride */
@@ -1392,7 +1393,8 @@ int cgpu_mapstate_sync(cgpu_ctx *ctx, const cgpu_l3_program *prog, const cgpu_la
  * there instead: IPv4 DROP with ret CGPU_DROP_INVALID (lib/l3.h:57-60), IPv6
  * TIME_EXCEEDED with the other outputs 0 (lib/l3.h:36-43).  Encapsulation
  * does not decrement.  The MAC rewrite, the decrement itself and checksums
- * are packet rewriting and not done here.
+ * are packet rewriting and not done here: cgpu_forward_frames, below, makes
+ * the same decision on raw frames and rewrites them.
  */
 #define CGPU_FWD_LXC 0u
 #define CGPU_FWD_NETDEV 1u
@@ -1450,6 +1452,86 @@ int cgpu_forward_v6(cgpu_ctx *ctx, const cgpu_fwd_params *params, const cgpu_fwd
  * a key (all 0 otherwise: the snapshot's endpoint sets answer), and are no
  * part of cgpu_table_bytes, cgpu_table_verify or the upload check. */
 int cgpu_forward_table_bytes(cgpu_ctx *ctx, uint64_t *out);
+
+/*
+ * The forwarding step on raw frames: per frame of a mixed IPv4 / IPv6 batch
+ * (the slots of cgpu_frames) the decision of cgpu_forward_v4 / _v6 on the
+ * frame's own daddr and ttl / hop limit and, with CGPU_FWDF_REWRITE, that
+ * branch's L2 / L3 rewrite in the frame's slot (ipv4_l3 / ipv6_l3,
+ * bpf/lib/l3.h:31-69, with ipv4_dec_ttl, lib/ipv4.h:30-43, and
+ * ipv6_dec_hoplimit, lib/ipv6.h:178-193; the call sites bpf_lxc.c:563, 629,
+ * 643, 258, 337, 351 and lib/l3.h:83, 114).
+ *
+ * Per frame:
+ *   a. ethertype (bytes 12..13) 0x0800: IPv4, 0x86DD: IPv6; any other, or a
+ *      frame whose min(len, stride) does not cover 14 + 20 (IPv4) / 14 + 40
+ *      (IPv6) bytes: NONE, all outputs 0, the frame untouched;
+ *   b. CGPU_FWD_LXC only: stage == 7 (NOT_CLASSIFIED, the responders' frames,
+ *      whose verdict is 0): NONE; then the list of cgpu_forward_v4 as written
+ *      (no CGPU_F_EGRESS: NONE; verdict < 0, the parse drops and
+ *      CGPU_DROP_SNAPLEN among them: DROP, ret = verdict);
+ *   c. daddr = bytes 30..33 (IPv4, the u32 as loaded) / 38..53 (IPv6), ttl =
+ *      byte 22 / hop limit = byte 21; action, ret, ifindex and arg are what
+ *      cgpu_forward_v4 / _v6 return for these columns, the expired-ttl rule
+ *      included;
+ *   d. CGPU_FWDF_REWRITE, by the final action (any other keeps every byte:
+ *      encapsulation does not decrement, an expired frame is not touched):
+ *        PROXY, HOST (LXC)   smac = cgpu_config.node_mac (NODE_MAC,
+ *                            bpf_lxc.c:87, 411), dmac = host_mac, decrement
+ *        LOCAL               smac = the endpoint's node_mac, dmac = its mac
+ *                            (the first six bytes, as stored, of the 8-byte
+ *                            fields: eth_store_saddr(skb, (__u8 *)&router_mac,
+ *                            0)), decrement; all-zero MACs while no endpoint
+ *                            has a non-zero value
+ *        STACK, CGPU_FWD_LXC smac unchanged, dmac = node_mac, decrement
+ *        STACK, NETDEV       nothing (TC_ACT_OK, bpf_netdev.c:427, 452)
+ *      dmac is bytes 0..5, smac bytes 6..11.  The IPv4 decrement stores
+ *      ttl - 1 at byte 22 and patches the checksum as the kernel's
+ *      bpf_l3_csum_replace(.., from = ttl, to = ttl - 1, 2) does: with c the
+ *      u16 at bytes 24..25 (little-endian load) and add(a, b) = (r = a + b,
+ *      r + (r < b)) in u32, t = add(add(~c, ~ttl), ttl - 1), folded twice by
+ *      t = (t & 0xffff) + (t >> 16), and (u16)~t stored back.  Nothing is
+ *      verified: an invalid checksum gets the same delta.  IPv6 decrements
+ *      byte 21 and changes nothing else.
+ *
+ * Not modelled: the proxy's L4 port rewrite and its checksum
+ * (ipv4_redirect_to_host_port), ipv6_store_flowlabel on the IPv6 egress STACK
+ * branch (bpf_lxc.c:355), rewrite_dmac_to_host (bpf_netdev.c:165),
+ * DROP_WRITE_ERROR, LXC_NAT46, the tunnel header of an OVERLAY frame, and an
+ * ipcache tunnel lookup inside the call (the caller hands in a `tunnel` column
+ * or none).
+ *
+ * -EINVAL, judged before the context, for a null struct, a null required
+ * column, a bad mode, unknown flag bits, nonzero reserved or pad, a misaligned
+ * 4-byte column, a stride that is not a multiple of 16 or is below 64, or data
+ * that is not 16-byte aligned; -ENODEV on a host-only context; n == 0 is a
+ * no-op.  One snapshot serves the whole batch.  The endpoints' MACs sit in
+ * device arrays beside the forwarding tables (16 B per table slot), which
+ * cgpu_forward_table_bytes does not report.
+ */
+#define CGPU_FWDF_REWRITE 1u
+
+typedef struct cgpu_fwdf_params {
+	cgpu_fwd_params fwd;  /* mode, CGPU_FWD_ENCAP, ipv4_mask, host_ifindex, encap_ifindex; reserved 0 */
+	uint8_t host_mac[6];  /* HOST_IFINDEX_MAC (bpf/node_config.h:39) */
+	uint8_t pad[2];       /* must be 0 */
+	uint32_t flags;       /* CGPU_FWDF_REWRITE */
+	uint32_t reserved[3]; /* must be 0 */
+} cgpu_fwdf_params;
+
+typedef struct cgpu_fwdf_in { /* device pointers */
+	uint8_t *data;          /* the slots of cgpu_frames (same stride / alignment rules);
+				   written only with CGPU_FWDF_REWRITE */
+	const uint32_t *len;
+	const uint8_t *flags;   /* CGPU_F_EGRESS; NULL only in NETDEV mode */
+	uint32_t stride, reserved;
+	const int32_t *verdict; /* cgpu_classify_frames' verdict; NULL only in NETDEV mode */
+	const uint8_t *stage;   /* its stage; NULL only in NETDEV mode */
+	const uint32_t *tunnel; /* raw tunnel_endpoint word per frame; NULL = all 0 */
+} cgpu_fwdf_in;
+
+int cgpu_forward_frames(cgpu_ctx *ctx, const cgpu_fwdf_params *params, const cgpu_fwdf_in *in, size_t n,
+			const cgpu_fwd_out *out, void *stream);
 
 /* ------------------------------------------------------------------ */
 /* local delivery: the destination endpoint's ingress policy           */
