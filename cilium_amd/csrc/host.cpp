@@ -28,6 +28,7 @@
 #include <thread>
 #include <set>
 #include <string>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -933,9 +934,44 @@ static std::array<uint32_t, 8> v6t_rec64(V6Build &b, uint64_t top, const std::ve
 
 uint32_t h64_home(const std::array<uint32_t, 8> &r) { return mix32(r[0], r[1]); }
 
-template <size_t W>
-void hop_place(std::vector<std::array<uint32_t, W>> &tab, uint32_t &mask,
-	       const std::vector<std::array<uint32_t, W>> &recs, uint32_t (*home_of)(const std::array<uint32_t, W> &));
+/* Rows of W words into a single-slot neighbourhood hash (tables.h cover6's
+ * h64 with word 3 and COVER6_USED, fwd_tables with FWD_USED): first fit
+ * within POL_HOP slots of the home slot, the table doubled until every row
+ * fits.  Word T of a slot becomes USED plus, in its top byte, the hop bits of
+ * the rows whose home it is (whatever `rows` holds there is dropped); at
+ * (optional): the slot each row landed in. */
+template <size_t W, size_t T, uint32_t USED, class H>
+void hop_place(const std::vector<std::array<uint32_t, W>> &rows, H home_of,
+	       std::vector<std::array<uint32_t, W>> &tab, uint32_t &mask, std::vector<uint32_t> *at = nullptr)
+{
+	uint32_t nb = next_pow2(std::max<uint64_t>(64, 2 * rows.size()));
+	for (;; nb *= 2) {
+		tab.assign(nb, std::array<uint32_t, W>{});
+		mask = nb - 1;
+		if (at)
+			at->clear();
+		bool ok = true;
+		for (auto &r : rows) {
+			const uint32_t home = home_of(r) & mask;
+			uint32_t d = 0;
+			while (d < POL_HOP && (tab[(home + d) & mask][T] & USED))
+				d++;
+			if (d == POL_HOP) {
+				ok = false;
+				break;
+			}
+			auto &sl = tab[(home + d) & mask];
+			const uint32_t hop = sl[T] & ~POL_CTR_MASK;
+			sl = r;
+			sl[T] = hop | USED;
+			tab[home][T] |= 1u << (POL_HOP_SHIFT + d);
+			if (at)
+				at->push_back((home + d) & mask);
+		}
+		if (ok)
+			return;
+	}
+}
 
 /* Longest-prefix trie over (rank, len, address) candidates; see tables.h v6_lpm. */
 void build_v6(std::vector<Rank6> cand, V6Build &b, bool tun = false)
@@ -1090,7 +1126,7 @@ void build_v6(std::vector<Rank6> cand, V6Build &b, bool tun = false)
 		b.b24.insert(b.b24.end(), e24.begin(), e24.end());
 		i = j;
 	}
-	hop_place<8>(b.h64, b.m64, r64, h64_home);
+	hop_place<8, 3, COVER6_USED>(r64, h64_home, b.h64, b.m64);
 	/* the bloom of the /64s with records: ~2 records per 32-bit word (3
 	 * bits each) keeps false positives near 1 % */
 	{
@@ -1307,36 +1343,6 @@ uint32_t cover6_node64(Cover6Build &b, const std::vector<std::pair<uint64_t, uin
 	return COVER6_NODE << 30 | off;
 }
 
-template <size_t W>
-void hop_place(std::vector<std::array<uint32_t, W>> &tab, uint32_t &mask,
-	       const std::vector<std::array<uint32_t, W>> &recs, uint32_t (*home_of)(const std::array<uint32_t, W> &))
-{
-	uint32_t nb = next_pow2(std::max<uint64_t>(64, 2 * recs.size()));
-	for (;;) {
-		tab.assign(nb, std::array<uint32_t, W>{});
-		mask = nb - 1;
-		bool ok = true;
-		for (auto &r : recs) {
-			const uint32_t home = home_of(r) & mask;
-			uint32_t d = 0;
-			while (d < POL_HOP && (tab[(home + d) & mask][3] & COVER6_USED))
-				d++;
-			if (d == POL_HOP) {
-				ok = false;
-				break;
-			}
-			auto &sl = tab[(home + d) & mask];
-			const uint32_t hop = sl[3] & ~0xFFFFFFu;
-			sl = r;
-			sl[3] = hop | COVER6_USED;
-			tab[home][3] |= 1u << (POL_HOP_SHIFT + d);
-		}
-		if (ok)
-			return;
-		nb *= 2;
-	}
-}
-
 /* The /32 entry of the prefixes longer than /32 among ps[k, l) (one /32,
  * sorted; shorter ones are skipped): an interval node over bits 32..63
  * (/33../64) flagged deep when the /32 also has /64 records, or DEEP when only
@@ -1490,7 +1496,7 @@ void build_cover6(const std::vector<Rank6> &cand, Cover6Build &b)
 		b.b24.insert(b.b24.end(), e24.begin(), e24.end());
 		i = j;
 	}
-	hop_place<8>(b.h64, b.m64, r64, h64_home);
+	hop_place<8, 3, COVER6_USED>(r64, h64_home, b.h64, b.m64);
 	/* 8 zero units past the last node: the octet load of a node reads
 	 * 128 B from its start whatever its length */
 	b.pool.insert(b.pool.end(), 32, 0u);
@@ -1986,7 +1992,7 @@ struct cgpu_ctx {
 	 * tables (tables.h fwd_tables) a commit builds after a change of either map
 	 * or of the endpoint keys, and only while one of the two holds something */
 	std::map<std::array<uint8_t, 20>, cgpu_endpoint_info> lxc_info;
-	std::map<std::array<uint8_t, 20>, std::array<uint8_t, 20>> tun;
+	std::map<std::array<uint8_t, 20>, cgpu_endpoint_key> tun;
 	bool fwd_dirty = false, fwd_built = false;
 	/* cilium_lb4_services, keyed address << 32 | dport << 16 | slave so that
 	 * a frontend's entries are adjacent */
@@ -3053,85 +3059,6 @@ CGPU_EXPORT int cgpu_endpoint_lookup_info(cgpu_ctx *c, const cgpu_endpoint_key *
 	return 0;
 }
 
-/* ---- cilium_tunnel_map (bpf/lib/maps.h:92-101; the agent: pkg/maps/tunnel/
- * tunnel.go): a hash map, whole-key compare ---- */
-CGPU_EXPORT int cgpu_tunnel_update(cgpu_ctx *c, const cgpu_endpoint_key *key, const cgpu_endpoint_key *val,
-				   uint64_t flags)
-{
-	if (!c || !key || !val)
-		return fail(-EINVAL, "null argument");
-	if (int r = check_flags(flags))
-		return r;
-	std::array<uint8_t, 20> k, v;
-	memcpy(k.data(), key, 20);
-	memcpy(v.data(), val, 20);
-	std::lock_guard<std::mutex> g(c->mu);
-	auto it = c->tun.find(k);
-	if (it == c->tun.end()) {
-		if (flags == CGPU_EXIST)
-			return fail(-ENOENT, "tunnel key not present");
-		if (c->tun.size() >= CGPU_TUNNEL_MAP_SIZE)
-			return fail(-E2BIG, "tunnel map full (%u)", CGPU_TUNNEL_MAP_SIZE);
-		c->tun.emplace(k, v);
-	} else {
-		if (flags == CGPU_NOEXIST)
-			return fail(-EEXIST, "tunnel key exists");
-		it->second = v;
-	}
-	c->fwd_dirty = true;
-	return 0;
-}
-
-CGPU_EXPORT int cgpu_tunnel_delete(cgpu_ctx *c, const cgpu_endpoint_key *key)
-{
-	if (!c || !key)
-		return fail(-EINVAL, "null argument");
-	std::array<uint8_t, 20> k;
-	memcpy(k.data(), key, 20);
-	std::lock_guard<std::mutex> g(c->mu);
-	if (!c->tun.erase(k))
-		return -ENOENT;
-	c->fwd_dirty = true;
-	return 0;
-}
-
-CGPU_EXPORT int cgpu_tunnel_lookup(cgpu_ctx *c, const cgpu_endpoint_key *key, cgpu_endpoint_key *out)
-{
-	if (!c || !key || !out)
-		return fail(-EINVAL, "null argument");
-	std::array<uint8_t, 20> k;
-	memcpy(k.data(), key, 20);
-	std::lock_guard<std::mutex> g(c->mu);
-	auto it = c->tun.find(k);
-	if (it == c->tun.end())
-		return -ENOENT;
-	memcpy(out, it->second.data(), 20);
-	return 0;
-}
-
-CGPU_EXPORT int cgpu_tunnel_get_next_key(cgpu_ctx *c, const cgpu_endpoint_key *key, cgpu_endpoint_key *next)
-{
-	if (!c || !next)
-		return fail(-EINVAL, "null argument");
-	std::array<uint8_t, 20> k{};
-	if (key)
-		memcpy(k.data(), key, 20);
-	std::lock_guard<std::mutex> g(c->mu);
-	auto it = key ? c->tun.upper_bound(k) : c->tun.begin();
-	if (it == c->tun.end())
-		return -ENOENT;
-	memcpy(next, it->first.data(), 20);
-	return 0;
-}
-
-CGPU_EXPORT size_t cgpu_tunnel_count(cgpu_ctx *c)
-{
-	if (!c)
-		return 0;
-	std::lock_guard<std::mutex> g(c->mu);
-	return c->tun.size();
-}
-
 CGPU_EXPORT int cgpu_endpoint_delete(cgpu_ctx *c, const cgpu_endpoint_key *key)
 {
 	if (!c || !key)
@@ -3196,54 +3123,104 @@ CGPU_EXPORT int cgpu_lxc_lookup(cgpu_ctx *c, uint32_t ep, cgpu_lxc_info *out)
 }
 
 /* ======================================================================= */
-/* service map (pkg/maps/lbmap; bpf(2) htab semantics, whole-key compare)    */
+/* the mirror's plain hash maps (bpf(2) htab semantics, whole-key compare)   */
 /* ======================================================================= */
-static inline uint64_t lb_mkey(const cgpu_lb4_key *k)
-{
-	return (uint64_t)k->address << 32 | (uint64_t)k->dport << 16 | k->slave;
-}
+/* cilium_lb4_services / cilium_lb6_services (pkg/maps/lbmap), their
+ * reverse-NAT maps (lb.h:54-68; lbmap.go:229-260) and cilium_tunnel_map
+ * (bpf/lib/maps.h:92-101; pkg/maps/tunnel/tunnel.go) keep one contract, the
+ * htab_* templates below.  A family F names what differs: K and V, the ABI's
+ * key and value; map(), the std::map it lives in, whose order is the
+ * get_next_key order; mkey() / unkey() between K and that map's key; cap(),
+ * the capacity; touch(), what a change marks for the next commit; and the
+ * nouns of its messages. */
+struct Lb4Tab {
+	typedef cgpu_lb4_key K;
+	typedef cgpu_lb4_service V;
+	static constexpr const char *key_noun = "lb4 key", *map_noun = "lb4 service map";
+	static std::map<uint64_t, V> &map(cgpu_ctx *c) { return c->lb; }
+	static uint64_t mkey(const K &k) { return (uint64_t)k.address << 32 | (uint64_t)k.dport << 16 | k.slave; }
+	static K unkey(uint64_t m) { return K{(uint32_t)(m >> 32), (uint16_t)(m >> 16), (uint16_t)m}; }
+	static uint32_t cap(const cgpu_ctx *c) { return c->cfg.lb_max_entries; }
+	static void touch(cgpu_ctx *c) { c->dirty |= 1u << G_LB; }
+};
 
-static inline cgpu_lb4_key lb_unkey(uint64_t m)
-{
-	cgpu_lb4_key k;
-	k.address = (uint32_t)(m >> 32);
-	k.dport = (uint16_t)(m >> 16);
-	k.slave = (uint16_t)m;
-	return k;
-}
+struct Lb6Tab {
+	typedef cgpu_lb6_key K;
+	typedef cgpu_lb6_service V;
+	static constexpr const char *key_noun = "lb6 key", *map_noun = "lb6 service map";
+	static std::map<Lb6K, V> &map(cgpu_ctx *c) { return c->lb6; }
+	static Lb6K mkey(const K &k) { return lb6_mkey(&k); }
+	static K unkey(const Lb6K &m) { return lb6_unkey(m); }
+	static uint32_t cap(const cgpu_ctx *c) { return c->cfg.lb_max_entries; }
+	static void touch(cgpu_ctx *c) { c->dirty |= 1u << G_LB6; }
+};
 
-static int lb_put(cgpu_ctx *c, const cgpu_lb4_key *key, const cgpu_lb4_service *val, uint64_t flags)
+/* keyed by the raw index word; as many entries as the service maps */
+template <class Val> struct RnTab {
+	typedef uint16_t K;
+	typedef Val V;
+	static uint16_t mkey(uint16_t index) { return index; }
+	static uint16_t unkey(uint16_t m) { return m; }
+	static uint32_t cap(const cgpu_ctx *c) { return c->cfg.lb_max_entries; }
+};
+
+struct Rn4Tab : RnTab<cgpu_lb4_reverse_nat> {
+	static constexpr const char *key_noun = "lb4 reverse NAT index", *map_noun = "lb4 reverse NAT map";
+	static std::map<uint16_t, V> &map(cgpu_ctx *c) { return c->rn4; }
+	static void touch(cgpu_ctx *c) { c->rn4_dirty = true; }
+};
+
+struct Rn6Tab : RnTab<cgpu_lb6_reverse_nat> {
+	static constexpr const char *key_noun = "lb6 reverse NAT index", *map_noun = "lb6 reverse NAT map";
+	static std::map<uint16_t, V> &map(cgpu_ctx *c) { return c->rn6; }
+	static void touch(cgpu_ctx *c) { c->rn6_dirty = true; }
+};
+
+struct TunTab {
+	typedef cgpu_endpoint_key K;
+	typedef cgpu_endpoint_key V;
+	static constexpr const char *key_noun = "tunnel key", *map_noun = "tunnel map";
+	static std::map<std::array<uint8_t, 20>, V> &map(cgpu_ctx *c) { return c->tun; }
+	static std::array<uint8_t, 20> mkey(const K &k)
+	{
+		std::array<uint8_t, 20> m;
+		memcpy(m.data(), &k, 20);
+		return m;
+	}
+	static K unkey(const std::array<uint8_t, 20> &m)
+	{
+		K k;
+		memcpy(&k, m.data(), 20);
+		return k;
+	}
+	static uint32_t cap(const cgpu_ctx *) { return CGPU_TUNNEL_MAP_SIZE; }
+	static void touch(cgpu_ctx *c) { c->fwd_dirty = true; }
+};
+
+/* one update; caller holds mu and has checked the flags */
+template <class F> static int htab_put(cgpu_ctx *c, const typename F::K &key, const typename F::V &val, uint64_t flags)
 {
-	const uint64_t m = lb_mkey(key);
-	auto it = c->lb.find(m);
-	if (it == c->lb.end()) {
+	auto &m = F::map(c);
+	const auto k = F::mkey(key);
+	auto it = m.find(k);
+	if (it == m.end()) {
 		if (flags == CGPU_EXIST)
-			return fail(-ENOENT, "lb4 key not present");
-		if (c->lb.size() >= c->cfg.lb_max_entries)
-			return fail(-E2BIG, "lb4 service map full (%u)", c->cfg.lb_max_entries);
-		c->lb.emplace(m, *val);
+			return fail(-ENOENT, "%s not present", F::key_noun);
+		if (m.size() >= F::cap(c))
+			return fail(-E2BIG, "%s full (%u)", F::map_noun, F::cap(c));
+		m.emplace(k, val);
 	} else {
 		if (flags == CGPU_NOEXIST)
-			return fail(-EEXIST, "lb4 key exists");
-		it->second = *val;
+			return fail(-EEXIST, "%s exists", F::key_noun);
+		it->second = val;
 	}
-	c->dirty |= 1u << G_LB;
+	F::touch(c);
 	return 0;
 }
 
-CGPU_EXPORT int cgpu_lb4_update(cgpu_ctx *c, const cgpu_lb4_key *key, const cgpu_lb4_service *val,
-				uint64_t flags)
-{
-	if (!c || !key || !val)
-		return fail(-EINVAL, "null argument");
-	if (int r = check_flags(flags))
-		return r;
-	std::lock_guard<std::mutex> g(c->mu);
-	return lb_put(c, key, val, flags);
-}
-
-CGPU_EXPORT int cgpu_lb4_update_batch(cgpu_ctx *c, const cgpu_lb4_key *keys,
-				      const cgpu_lb4_service *vals, size_t n, uint64_t flags)
+/* the calls themselves; a missing key is a bare -ENOENT (no message) */
+template <class F>
+static int htab_update(cgpu_ctx *c, const typename F::K *keys, const typename F::V *vals, size_t n, uint64_t flags)
 {
 	if (!c || (n && (!keys || !vals)))
 		return fail(-EINVAL, "null argument");
@@ -3251,163 +3228,151 @@ CGPU_EXPORT int cgpu_lb4_update_batch(cgpu_ctx *c, const cgpu_lb4_key *keys,
 		return r;
 	std::lock_guard<std::mutex> g(c->mu);
 	for (size_t i = 0; i < n; i++)
-		if (int r = lb_put(c, &keys[i], &vals[i], flags))
+		if (int r = htab_put<F>(c, keys[i], vals[i], flags))
 			return r;
 	return 0;
 }
 
-CGPU_EXPORT int cgpu_lb4_delete(cgpu_ctx *c, const cgpu_lb4_key *key)
+template <class F>
+static int htab_update(cgpu_ctx *c, const typename F::K *key, const typename F::V *val, uint64_t flags)
+{
+	return c && key && val ? htab_update<F>(c, key, val, 1, flags) : fail(-EINVAL, "null argument");
+}
+
+template <class F> static int htab_delete(cgpu_ctx *c, const typename F::K *key)
 {
 	if (!c || !key)
 		return fail(-EINVAL, "null argument");
 	std::lock_guard<std::mutex> g(c->mu);
-	if (!c->lb.erase(lb_mkey(key)))
+	if (!F::map(c).erase(F::mkey(*key)))
 		return -ENOENT;
-	c->dirty |= 1u << G_LB;
+	F::touch(c);
 	return 0;
 }
 
-CGPU_EXPORT int cgpu_lb4_lookup(cgpu_ctx *c, const cgpu_lb4_key *key, cgpu_lb4_service *out)
+template <class F> static int htab_lookup(cgpu_ctx *c, const typename F::K *key, typename F::V *out)
 {
 	if (!c || !key || !out)
 		return fail(-EINVAL, "null argument");
 	std::lock_guard<std::mutex> g(c->mu);
-	auto it = c->lb.find(lb_mkey(key));
-	if (it == c->lb.end())
+	auto &m = F::map(c);
+	auto it = m.find(F::mkey(*key));
+	if (it == m.end())
 		return -ENOENT;
 	*out = it->second;
 	return 0;
 }
 
-CGPU_EXPORT int cgpu_lb4_get_next_key(cgpu_ctx *c, const cgpu_lb4_key *key, cgpu_lb4_key *next)
+/* key == NULL: the first key; else the next larger one, present or not */
+template <class F> static int htab_next(cgpu_ctx *c, const typename F::K *key, typename F::K *next)
 {
 	if (!c || !next)
 		return fail(-EINVAL, "null argument");
 	std::lock_guard<std::mutex> g(c->mu);
-	auto it = key ? c->lb.upper_bound(lb_mkey(key)) : c->lb.begin();
-	if (it == c->lb.end())
+	auto &m = F::map(c);
+	auto it = key ? m.upper_bound(F::mkey(*key)) : m.begin();
+	if (it == m.end())
 		return -ENOENT;
-	*next = lb_unkey(it->first);
+	*next = F::unkey(it->first);
 	return 0;
 }
 
-CGPU_EXPORT size_t cgpu_lb4_count(cgpu_ctx *c)
+template <class F> static size_t htab_count(cgpu_ctx *c)
 {
 	if (!c)
 		return 0;
 	std::lock_guard<std::mutex> g(c->mu);
-	return c->lb.size();
+	return F::map(c).size();
 }
 
-/* ---- cilium_lb4_reverse_nat / cilium_lb6_reverse_nat (lb.h:54-68; the agent:
- * pkg/maps/lbmap/lbmap.go:229-260) ---- */
-template <class V>
-static int rn_put(cgpu_ctx *c, std::map<uint16_t, V> &m, bool &dirty, uint16_t index, const V *val,
-		  uint64_t flags, const char *what)
+CGPU_EXPORT int cgpu_lb4_update(cgpu_ctx *c, const cgpu_lb4_key *key, const cgpu_lb4_service *val,
+				uint64_t flags)
 {
-	if (!c || !val)
-		return fail(-EINVAL, "null argument");
-	if (int r = check_flags(flags))
-		return r;
-	std::lock_guard<std::mutex> g(c->mu);
-	auto it = m.find(index);
-	if (it == m.end()) {
-		if (flags == CGPU_EXIST)
-			return fail(-ENOENT, "%s index not present", what);
-		if (m.size() >= c->cfg.lb_max_entries)
-			return fail(-E2BIG, "%s map full (%u)", what, c->cfg.lb_max_entries);
-		m.emplace(index, *val);
-	} else {
-		if (flags == CGPU_NOEXIST)
-			return fail(-EEXIST, "%s index exists", what);
-		it->second = *val;
-	}
-	dirty = true;
-	return 0;
+	return htab_update<Lb4Tab>(c, key, val, flags);
 }
-
-template <class V> static int rn_del(cgpu_ctx *c, std::map<uint16_t, V> &m, bool &dirty, uint16_t index)
+CGPU_EXPORT int cgpu_lb4_update_batch(cgpu_ctx *c, const cgpu_lb4_key *keys,
+				      const cgpu_lb4_service *vals, size_t n, uint64_t flags)
 {
-	if (!c)
-		return fail(-EINVAL, "null argument");
-	std::lock_guard<std::mutex> g(c->mu);
-	if (!m.erase(index))
-		return -ENOENT;
-	dirty = true;
-	return 0;
+	return htab_update<Lb4Tab>(c, keys, vals, n, flags);
 }
-
-template <class V> static int rn_get(cgpu_ctx *c, std::map<uint16_t, V> &m, uint16_t index, V *out)
+CGPU_EXPORT int cgpu_lb4_delete(cgpu_ctx *c, const cgpu_lb4_key *key) { return htab_delete<Lb4Tab>(c, key); }
+CGPU_EXPORT int cgpu_lb4_lookup(cgpu_ctx *c, const cgpu_lb4_key *key, cgpu_lb4_service *out)
 {
-	if (!c || !out)
-		return fail(-EINVAL, "null argument");
-	std::lock_guard<std::mutex> g(c->mu);
-	auto it = m.find(index);
-	if (it == m.end())
-		return -ENOENT;
-	*out = it->second;
-	return 0;
+	return htab_lookup<Lb4Tab>(c, key, out);
 }
-
-template <class V>
-static int rn_next(cgpu_ctx *c, std::map<uint16_t, V> &m, const uint16_t *index, uint16_t *next)
+CGPU_EXPORT int cgpu_lb4_get_next_key(cgpu_ctx *c, const cgpu_lb4_key *key, cgpu_lb4_key *next)
 {
-	if (!c || !next)
-		return fail(-EINVAL, "null argument");
-	std::lock_guard<std::mutex> g(c->mu);
-	auto it = index ? m.upper_bound(*index) : m.begin();
-	if (it == m.end())
-		return -ENOENT;
-	*next = it->first;
-	return 0;
+	return htab_next<Lb4Tab>(c, key, next);
 }
+CGPU_EXPORT size_t cgpu_lb4_count(cgpu_ctx *c) { return htab_count<Lb4Tab>(c); }
 
+CGPU_EXPORT int cgpu_lb6_update(cgpu_ctx *c, const cgpu_lb6_key *key, const cgpu_lb6_service *val,
+				uint64_t flags)
+{
+	return htab_update<Lb6Tab>(c, key, val, flags);
+}
+CGPU_EXPORT int cgpu_lb6_update_batch(cgpu_ctx *c, const cgpu_lb6_key *keys,
+				      const cgpu_lb6_service *vals, size_t n, uint64_t flags)
+{
+	return htab_update<Lb6Tab>(c, keys, vals, n, flags);
+}
+CGPU_EXPORT int cgpu_lb6_delete(cgpu_ctx *c, const cgpu_lb6_key *key) { return htab_delete<Lb6Tab>(c, key); }
+CGPU_EXPORT int cgpu_lb6_lookup(cgpu_ctx *c, const cgpu_lb6_key *key, cgpu_lb6_service *out)
+{
+	return htab_lookup<Lb6Tab>(c, key, out);
+}
+CGPU_EXPORT int cgpu_lb6_get_next_key(cgpu_ctx *c, const cgpu_lb6_key *key, cgpu_lb6_key *next)
+{
+	return htab_next<Lb6Tab>(c, key, next);
+}
+CGPU_EXPORT size_t cgpu_lb6_count(cgpu_ctx *c) { return htab_count<Lb6Tab>(c); }
+
+/* (the index travels by value: its address is never null) */
 CGPU_EXPORT int cgpu_revnat4_update(cgpu_ctx *c, uint16_t index, const cgpu_lb4_reverse_nat *val, uint64_t flags)
 {
-	return c ? rn_put(c, c->rn4, c->rn4_dirty, index, val, flags, "lb4 reverse NAT") : fail(-EINVAL, "null argument");
+	return htab_update<Rn4Tab>(c, &index, val, flags);
 }
-CGPU_EXPORT int cgpu_revnat4_delete(cgpu_ctx *c, uint16_t index)
-{
-	return c ? rn_del(c, c->rn4, c->rn4_dirty, index) : fail(-EINVAL, "null argument");
-}
+CGPU_EXPORT int cgpu_revnat4_delete(cgpu_ctx *c, uint16_t index) { return htab_delete<Rn4Tab>(c, &index); }
 CGPU_EXPORT int cgpu_revnat4_lookup(cgpu_ctx *c, uint16_t index, cgpu_lb4_reverse_nat *val_out)
 {
-	return c ? rn_get(c, c->rn4, index, val_out) : fail(-EINVAL, "null argument");
+	return htab_lookup<Rn4Tab>(c, &index, val_out);
 }
 CGPU_EXPORT int cgpu_revnat4_get_next_key(cgpu_ctx *c, const uint16_t *index, uint16_t *next_out)
 {
-	return c ? rn_next(c, c->rn4, index, next_out) : fail(-EINVAL, "null argument");
+	return htab_next<Rn4Tab>(c, index, next_out);
 }
-CGPU_EXPORT size_t cgpu_revnat4_count(cgpu_ctx *c)
-{
-	if (!c)
-		return 0;
-	std::lock_guard<std::mutex> g(c->mu);
-	return c->rn4.size();
-}
+CGPU_EXPORT size_t cgpu_revnat4_count(cgpu_ctx *c) { return htab_count<Rn4Tab>(c); }
+
 CGPU_EXPORT int cgpu_revnat6_update(cgpu_ctx *c, uint16_t index, const cgpu_lb6_reverse_nat *val, uint64_t flags)
 {
-	return c ? rn_put(c, c->rn6, c->rn6_dirty, index, val, flags, "lb6 reverse NAT") : fail(-EINVAL, "null argument");
+	return htab_update<Rn6Tab>(c, &index, val, flags);
 }
-CGPU_EXPORT int cgpu_revnat6_delete(cgpu_ctx *c, uint16_t index)
-{
-	return c ? rn_del(c, c->rn6, c->rn6_dirty, index) : fail(-EINVAL, "null argument");
-}
+CGPU_EXPORT int cgpu_revnat6_delete(cgpu_ctx *c, uint16_t index) { return htab_delete<Rn6Tab>(c, &index); }
 CGPU_EXPORT int cgpu_revnat6_lookup(cgpu_ctx *c, uint16_t index, cgpu_lb6_reverse_nat *val_out)
 {
-	return c ? rn_get(c, c->rn6, index, val_out) : fail(-EINVAL, "null argument");
+	return htab_lookup<Rn6Tab>(c, &index, val_out);
 }
 CGPU_EXPORT int cgpu_revnat6_get_next_key(cgpu_ctx *c, const uint16_t *index, uint16_t *next_out)
 {
-	return c ? rn_next(c, c->rn6, index, next_out) : fail(-EINVAL, "null argument");
+	return htab_next<Rn6Tab>(c, index, next_out);
 }
-CGPU_EXPORT size_t cgpu_revnat6_count(cgpu_ctx *c)
+CGPU_EXPORT size_t cgpu_revnat6_count(cgpu_ctx *c) { return htab_count<Rn6Tab>(c); }
+
+CGPU_EXPORT int cgpu_tunnel_update(cgpu_ctx *c, const cgpu_endpoint_key *key, const cgpu_endpoint_key *val,
+				   uint64_t flags)
 {
-	if (!c)
-		return 0;
-	std::lock_guard<std::mutex> g(c->mu);
-	return c->rn6.size();
+	return htab_update<TunTab>(c, key, val, flags);
 }
+CGPU_EXPORT int cgpu_tunnel_delete(cgpu_ctx *c, const cgpu_endpoint_key *key) { return htab_delete<TunTab>(c, key); }
+CGPU_EXPORT int cgpu_tunnel_lookup(cgpu_ctx *c, const cgpu_endpoint_key *key, cgpu_endpoint_key *out)
+{
+	return htab_lookup<TunTab>(c, key, out);
+}
+CGPU_EXPORT int cgpu_tunnel_get_next_key(cgpu_ctx *c, const cgpu_endpoint_key *key, cgpu_endpoint_key *next)
+{
+	return htab_next<TunTab>(c, key, next);
+}
+CGPU_EXPORT size_t cgpu_tunnel_count(cgpu_ctx *c) { return htab_count<TunTab>(c); }
 
 /* The reverse-NAT maps' device form (a commit, after a change): dense by the
  * raw index, IPv4 65,536 x 8 B {address, port | 1 << 16}, IPv6 65,536 x 32 B
@@ -3452,93 +3417,6 @@ static int rn_upload(cgpu_ctx *c)
 		c->rn6_dirty = false;
 	}
 	return 0;
-}
-
-static int lb6_put(cgpu_ctx *c, const cgpu_lb6_key *key, const cgpu_lb6_service *val, uint64_t flags)
-{
-	const Lb6K m = lb6_mkey(key);
-	auto it = c->lb6.find(m);
-	if (it == c->lb6.end()) {
-		if (flags == CGPU_EXIST)
-			return fail(-ENOENT, "lb6 key not present");
-		if (c->lb6.size() >= c->cfg.lb_max_entries)
-			return fail(-E2BIG, "lb6 service map full (%u)", c->cfg.lb_max_entries);
-		c->lb6.emplace(m, *val);
-	} else {
-		if (flags == CGPU_NOEXIST)
-			return fail(-EEXIST, "lb6 key exists");
-		it->second = *val;
-	}
-	c->dirty |= 1u << G_LB6;
-	return 0;
-}
-
-CGPU_EXPORT int cgpu_lb6_update(cgpu_ctx *c, const cgpu_lb6_key *key, const cgpu_lb6_service *val,
-				uint64_t flags)
-{
-	if (!c || !key || !val)
-		return fail(-EINVAL, "null argument");
-	if (int r = check_flags(flags))
-		return r;
-	std::lock_guard<std::mutex> g(c->mu);
-	return lb6_put(c, key, val, flags);
-}
-
-CGPU_EXPORT int cgpu_lb6_update_batch(cgpu_ctx *c, const cgpu_lb6_key *keys,
-				      const cgpu_lb6_service *vals, size_t n, uint64_t flags)
-{
-	if (!c || (n && (!keys || !vals)))
-		return fail(-EINVAL, "null argument");
-	if (int r = check_flags(flags))
-		return r;
-	std::lock_guard<std::mutex> g(c->mu);
-	for (size_t i = 0; i < n; i++)
-		if (int r = lb6_put(c, &keys[i], &vals[i], flags))
-			return r;
-	return 0;
-}
-
-CGPU_EXPORT int cgpu_lb6_delete(cgpu_ctx *c, const cgpu_lb6_key *key)
-{
-	if (!c || !key)
-		return fail(-EINVAL, "null argument");
-	std::lock_guard<std::mutex> g(c->mu);
-	if (!c->lb6.erase(lb6_mkey(key)))
-		return -ENOENT;
-	c->dirty |= 1u << G_LB6;
-	return 0;
-}
-
-CGPU_EXPORT int cgpu_lb6_lookup(cgpu_ctx *c, const cgpu_lb6_key *key, cgpu_lb6_service *out)
-{
-	if (!c || !key || !out)
-		return fail(-EINVAL, "null argument");
-	std::lock_guard<std::mutex> g(c->mu);
-	auto it = c->lb6.find(lb6_mkey(key));
-	if (it == c->lb6.end())
-		return -ENOENT;
-	*out = it->second;
-	return 0;
-}
-
-CGPU_EXPORT int cgpu_lb6_get_next_key(cgpu_ctx *c, const cgpu_lb6_key *key, cgpu_lb6_key *next)
-{
-	if (!c || !next)
-		return fail(-EINVAL, "null argument");
-	std::lock_guard<std::mutex> g(c->mu);
-	auto it = key ? c->lb6.upper_bound(lb6_mkey(key)) : c->lb6.begin();
-	if (it == c->lb6.end())
-		return -ENOENT;
-	*next = lb6_unkey(it->first);
-	return 0;
-}
-
-CGPU_EXPORT size_t cgpu_lb6_count(cgpu_ctx *c)
-{
-	if (!c)
-		return 0;
-	std::lock_guard<std::mutex> g(c->mu);
-	return c->lb6.size();
 }
 
 CGPU_EXPORT uint32_t cgpu_flow_hash6(const uint8_t *saddr16, const uint8_t *daddr16, uint16_t sport,
@@ -3599,7 +3477,7 @@ struct CommitIn {
 	 * the tunnel map; both empty = the tables go away */
 	bool fwd = false;
 	std::vector<std::pair<std::array<uint8_t, 20>, cgpu_endpoint_info>> fwd_ep;
-	std::vector<std::pair<std::array<uint8_t, 20>, std::array<uint8_t, 20>>> fwd_tun;
+	std::vector<std::pair<std::array<uint8_t, 20>, cgpu_endpoint_key>> fwd_tun;
 };
 
 
@@ -4311,44 +4189,6 @@ static int commit_lxc(cgpu_ctx *c, CommitIn &in, cgpu_snapshot &s, DevBufP &buf)
 	return 0;
 }
 
-/* rows of W words into a single-slot neighbourhood hash (tables.h fwd_tables):
- * first fit within POL_HOP slots of the home slot, the table doubled until
- * every row fits; word T of a slot is FWD_USED | hop << 24 (0 in `rows`);
- * at (optional): the slot each row landed in */
-template <size_t W, size_t T, class H>
-static void build_hop(const std::vector<std::array<uint32_t, W>> &rows, H home_of,
-		      std::vector<std::array<uint32_t, W>> &out, uint32_t &mask,
-		      std::vector<uint32_t> *at = nullptr)
-{
-	uint32_t nb = next_pow2(std::max<uint64_t>(64, 2 * rows.size()));
-	for (;; nb *= 2) {
-		out.assign(nb, std::array<uint32_t, W>{});
-		mask = nb - 1;
-		if (at)
-			at->clear();
-		bool ok = true;
-		for (auto &r : rows) {
-			const uint32_t home = home_of(r) & mask;
-			uint32_t d = 0;
-			while (d < POL_HOP && (out[(home + d) & mask][T] & FWD_USED))
-				d++;
-			if (d == POL_HOP) {
-				ok = false;
-				break;
-			}
-			auto &sl = out[(home + d) & mask];
-			const uint32_t hop = sl[T] & ~POL_CTR_MASK;
-			sl = r;
-			sl[T] = hop | FWD_USED;
-			out[home][T] |= 1u << (POL_HOP_SHIFT + d);
-			if (at)
-				at->push_back((home + d) & mask);
-		}
-		if (ok)
-			return;
-	}
-}
-
 /* the forwarding tables (tables.h fwd_tables) from every endpoint with its
  * value and the tunnel map; nothing to build: the snapshot has none */
 static int commit_fwd(cgpu_ctx *c, CommitIn &in, Epoch &e)
@@ -4394,21 +4234,21 @@ static int commit_fwd(cgpu_ctx *c, CommitIn &in, Epoch &e)
 		}
 	}
 	for (auto &kv : in.fwd_tun) {
-		sum += fnv(fnv(41, kv.first.data(), 20), kv.second.data(), 20);
+		sum += fnv(fnv(41, kv.first.data(), 20), &kv.second, 20);
 		uint32_t w[4], ip4;
 		const uint32_t fam = words(kv.first, w);
-		memcpy(&ip4, kv.second.data(), 4); /* tunnel->ip4 is all the datapath reads */
+		memcpy(&ip4, kv.second.ip, 4); /* tunnel->ip4 is all the datapath reads */
 		if (fam == 1 && !w[1] && !w[2] && !w[3])
 			t4.push_back({w[0], ip4, 0, 0});
 		else if (fam == 2 && !w[3])
 			t6.push_back({w[0], w[1], w[2], ip4, 0, 0, 0, 0});
 	}
 	fwd_tables f{};
-	build_hop<4, 3>(r4, [](const std::array<uint32_t, 4> &r) { return fwd_hash4(r[0]); }, o_e4, f.e4_mask, &at4);
-	build_hop<4, 3>(t4, [](const std::array<uint32_t, 4> &r) { return fwd_hash4(r[0]); }, o_t4, f.t4_mask);
-	build_hop<8, 6>(r6, [](const std::array<uint32_t, 8> &r) { return fold6(r[0], r[1], r[2], r[3]); }, o_e6,
+	hop_place<4, 3, FWD_USED>(r4, [](const std::array<uint32_t, 4> &r) { return fwd_hash4(r[0]); }, o_e4, f.e4_mask, &at4);
+	hop_place<4, 3, FWD_USED>(t4, [](const std::array<uint32_t, 4> &r) { return fwd_hash4(r[0]); }, o_t4, f.t4_mask);
+	hop_place<8, 6, FWD_USED>(r6, [](const std::array<uint32_t, 8> &r) { return fold6(r[0], r[1], r[2], r[3]); }, o_e6,
 			f.e6_mask, &at6);
-	build_hop<8, 6>(t6, [](const std::array<uint32_t, 8> &r) { return fold6(r[0], r[1], r[2], 0u); }, o_t6,
+	hop_place<8, 6, FWD_USED>(t6, [](const std::array<uint32_t, 8> &r) { return fold6(r[0], r[1], r[2], 0u); }, o_t6,
 			f.t6_mask);
 	/* the endpoints' MACs at the slot / row their key landed in (fwd_macs) */
 	std::vector<std::array<uint8_t, 16>> m4(o_e4.size(), std::array<uint8_t, 16>{}),
@@ -7286,44 +7126,73 @@ static int ct_classify(cgpu_ctx *c, const cgpu_snapshot &s, uint64_t *delta, CtM
 	return 0;
 }
 
-/* cgpu_classify_v4_ct; tunnel: NULL, or cgpu_classify_v4_ct_tun's output */
-/* the _rnat entry points' outputs into a launch (rn == NULL: none) */
-static void rnat4_into(ct_launch &a, const cgpu_rnat4_out *rn)
+/* The outputs of a stateful call: the loose pointers of the _ct forms (no
+ * daddr / dport) or a cgpu_ctlb_out / cgpu_ctlb6_out; and those of the _rnat
+ * forms (IPv6 has no daddr). */
+struct CtOuts {
+	int32_t *verdict;
+	uint8_t *ct_ret;
+	uint32_t *identity;
+	uint8_t *stage;
+	void *daddr;
+	uint16_t *dport;
+};
+
+struct CtRnat {
+	void *saddr;
+	uint32_t *daddr;
+	uint16_t *sport;
+	uint8_t *applied;
+};
+
+/* the ABI's structs as those two; `into`: the caller's storage; NULL stays NULL */
+template <class O> static const CtOuts *ct_outs(const O *out, CtOuts &into)
 {
-	if (!rn)
-		return;
-	a.rn_saddr = rn->saddr;
-	a.rn_daddr = rn->daddr;
-	a.rn_sport = rn->sport;
-	a.rn_applied = rn->applied;
+	if (!out)
+		return nullptr;
+	into = CtOuts{out->verdict, out->ct_ret, out->identity, out->stage, out->daddr, out->dport};
+	return &into;
 }
 
-static int rnat6_into(ct_launch &a, const cgpu_rnat6_out *rn)
+static const CtRnat *ct_rnat(const cgpu_rnat4_out *rn, CtRnat &into)
 {
 	if (!rn)
-		return 0;
-	if ((uintptr_t)rn->saddr & 15)
-		return fail(-EINVAL, "IPv6 address columns must be 16-byte aligned");
-	a.rn_saddr = rn->saddr;
-	a.rn_sport = rn->sport;
-	a.rn_applied = rn->applied;
-	return 0;
+		return nullptr;
+	into = CtRnat{rn->saddr, rn->daddr, rn->sport, rn->applied};
+	return &into;
 }
 
-static int classify_v4_ct(cgpu_ctx *c, const cgpu_tuples_v4_ct *t, size_t n, uint32_t now, int32_t *verdict,
-			  uint8_t *ct_ret, uint32_t *identity, uint8_t *stage, uint32_t *tunnel, void *stream,
-			  const cgpu_rnat4_out *rn = nullptr)
+static const CtRnat *ct_rnat(const cgpu_rnat6_out *rn, CtRnat &into)
 {
+	if (!rn)
+		return nullptr;
+	into = CtRnat{rn->saddr, nullptr, rn->sport, rn->applied};
+	return &into;
+}
+
+/* Every stateful entry point: T is cgpu_tuples_v4_ct or cgpu_tuples_v6_ct
+ * (the conntrack map follows it), svc the forms with the service step in
+ * front, tunnel the _tun forms' output (plain forms only), rn the _rnat
+ * forms'; NULL: none.  The order of the checks is part of the ABI. */
+template <class T>
+static int classify_ct(cgpu_ctx *c, const T *t, const uint32_t *hash, size_t n, uint32_t now, bool svc,
+		       const CtOuts *o, uint32_t *tunnel, const CtRnat *rn, void *stream)
+{
+	const bool v6 = std::is_same<T, cgpu_tuples_v6_ct>::value;
 	Pinned P;
 	if (int r = pin(c, stream, P))
 		return r;
-	if (!t || (n && (!t->saddr || !t->daddr || !t->sport || !t->dport || !t->proto || !t->l4 ||
-			 !t->flags || !t->len || !t->ep || !verdict || !ct_ret || !identity)))
+	if (!t || !o || (n && (!t->saddr || !t->daddr || !t->sport || !t->dport || !t->proto || !t->l4 ||
+			       !t->flags || !t->len || !t->ep || !o->verdict || !o->ct_ret || !o->identity)))
 		return fail(-EINVAL, "null tuple column or output");
-	if (n > (size_t)INT32_MAX)
-		return fail(-EINVAL, "batch of %zu packets exceeds 2^31 - 1", n);
+	if (v6 && n && (((uintptr_t)t->saddr | (uintptr_t)t->daddr | (uintptr_t)o->daddr) & 15))
+		return fail(-EINVAL, "IPv6 address columns must be 16-byte aligned");
+	if (n > (size_t)INT32_MAX / (svc ? 2 : 1))
+		return fail(-EINVAL, "batch of %zu packets exceeds 2^%d - 1", n, svc ? 30 : 31);
 	if (!n)
 		return 0;
+	if (v6 && rn && ((uintptr_t)rn->saddr & 15))
+		return fail(-EINVAL, "IPv6 address columns must be 16-byte aligned");
 	ct_launch a{};
 	a.saddr = t->saddr;
 	a.daddr = t->daddr;
@@ -7334,30 +7203,50 @@ static int classify_v4_ct(cgpu_ctx *c, const cgpu_tuples_v4_ct *t, size_t n, uin
 	a.flags = t->flags;
 	a.len = t->len;
 	a.ep = t->ep;
-	a.verdict = verdict;
-	a.ct_ret = ct_ret;
-	a.identity = identity;
-	a.stage = stage;
+	a.verdict = o->verdict;
+	a.ct_ret = o->ct_ret;
+	a.identity = o->identity;
+	a.stage = o->stage;
+	a.xdaddr = o->daddr;
+	a.xdport = o->dport;
+	a.hash = hash;
 	a.n = n;
 	a.now = now;
-	a.tunnel = tunnel;
-	a.tun = &P.tun();
-	rnat4_into(a, rn);
-	return ct_classify(c, P.snap(), P.delta, c->ct4, a, stream, false, rn != nullptr);
+	if (!svc) {
+		a.tunnel = tunnel;
+		a.tun = &P.tun();
+	}
+	if (rn) {
+		a.rn_saddr = rn->saddr;
+		a.rn_daddr = rn->daddr;
+		a.rn_sport = rn->sport;
+		a.rn_applied = rn->applied;
+	}
+	return ct_classify(c, P.snap(), P.delta, v6 ? c->ct6 : c->ct4, a, stream, svc, rn != nullptr);
 }
 
-CGPU_EXPORT int cgpu_classify_v4_ct_rnat(cgpu_ctx *c, const cgpu_tuples_v4_ct *t, size_t n, uint32_t now,
-					 int32_t *verdict, uint8_t *ct_ret, uint32_t *identity,
-					 uint8_t *stage, const cgpu_rnat4_out *rn, void *stream)
+/* the plain forms, their outputs loose */
+template <class T>
+static int classify_ct_plain(cgpu_ctx *c, const T *t, size_t n, uint32_t now, int32_t *verdict, uint8_t *ct_ret,
+			     uint32_t *identity, uint8_t *stage, uint32_t *tunnel, const CtRnat *rn, void *stream)
 {
-	return classify_v4_ct(c, t, n, now, verdict, ct_ret, identity, stage, nullptr, stream, rn);
+	const CtOuts o{verdict, ct_ret, identity, stage, nullptr, nullptr};
+	return classify_ct(c, t, nullptr, n, now, false, &o, tunnel, rn, stream);
 }
 
 CGPU_EXPORT int cgpu_classify_v4_ct(cgpu_ctx *c, const cgpu_tuples_v4_ct *t, size_t n, uint32_t now,
 				    int32_t *verdict, uint8_t *ct_ret, uint32_t *identity,
 				    uint8_t *stage, void *stream)
 {
-	return classify_v4_ct(c, t, n, now, verdict, ct_ret, identity, stage, nullptr, stream);
+	return classify_ct_plain(c, t, n, now, verdict, ct_ret, identity, stage, nullptr, nullptr, stream);
+}
+
+CGPU_EXPORT int cgpu_classify_v4_ct_rnat(cgpu_ctx *c, const cgpu_tuples_v4_ct *t, size_t n, uint32_t now,
+					 int32_t *verdict, uint8_t *ct_ret, uint32_t *identity,
+					 uint8_t *stage, const cgpu_rnat4_out *rn, void *stream)
+{
+	CtRnat r;
+	return classify_ct_plain(c, t, n, now, verdict, ct_ret, identity, stage, nullptr, ct_rnat(rn, r), stream);
 }
 
 CGPU_EXPORT int cgpu_classify_v4_ct_tun(cgpu_ctx *c, const cgpu_tuples_v4_ct *t, size_t n, uint32_t now,
@@ -7366,163 +7255,38 @@ CGPU_EXPORT int cgpu_classify_v4_ct_tun(cgpu_ctx *c, const cgpu_tuples_v4_ct *t,
 {
 	if (int r = check_tunnel(c, tunnel))
 		return r;
-	return classify_v4_ct(c, t, n, now, verdict, ct_ret, identity, stage, tunnel, stream);
-}
-
-static int classify_v4_ctlb(cgpu_ctx *c, const cgpu_tuples_v4_ct *t, const uint32_t *hash, size_t n,
-			    uint32_t now, const cgpu_ctlb_out *out, const cgpu_rnat4_out *rn, void *stream)
-{
-	Pinned P;
-	if (int r = pin(c, stream, P))
-		return r;
-	if (!t || !out || (n && (!t->saddr || !t->daddr || !t->sport || !t->dport || !t->proto || !t->l4 ||
-				 !t->flags || !t->len || !t->ep || !out->verdict || !out->ct_ret ||
-				 !out->identity)))
-		return fail(-EINVAL, "null tuple column or output");
-	if (n > (size_t)INT32_MAX / 2)
-		return fail(-EINVAL, "batch of %zu packets exceeds 2^30 - 1", n);
-	if (!n)
-		return 0;
-	ct_launch a{};
-	a.saddr = t->saddr;
-	a.daddr = t->daddr;
-	a.sport = t->sport;
-	a.dport = t->dport;
-	a.proto = t->proto;
-	a.l4 = t->l4;
-	a.flags = t->flags;
-	a.len = t->len;
-	a.ep = t->ep;
-	a.verdict = out->verdict;
-	a.ct_ret = out->ct_ret;
-	a.identity = out->identity;
-	a.stage = out->stage;
-	a.xdaddr = out->daddr;
-	a.xdport = out->dport;
-	a.hash = hash;
-	a.n = n;
-	a.now = now;
-	rnat4_into(a, rn);
-	return ct_classify(c, P.snap(), P.delta, c->ct4, a, stream, true, rn != nullptr);
+	return classify_ct_plain(c, t, n, now, verdict, ct_ret, identity, stage, tunnel, nullptr, stream);
 }
 
 CGPU_EXPORT int cgpu_classify_v4_ctlb(cgpu_ctx *c, const cgpu_tuples_v4_ct *t, const uint32_t *hash,
 				      size_t n, uint32_t now, const cgpu_ctlb_out *out, void *stream)
 {
-	return classify_v4_ctlb(c, t, hash, n, now, out, nullptr, stream);
+	CtOuts o;
+	return classify_ct(c, t, hash, n, now, true, ct_outs(out, o), nullptr, nullptr, stream);
 }
 
 CGPU_EXPORT int cgpu_classify_v4_ctlb_rnat(cgpu_ctx *c, const cgpu_tuples_v4_ct *t, const uint32_t *hash,
 					   size_t n, uint32_t now, const cgpu_ctlb_out *out,
 					   const cgpu_rnat4_out *rn, void *stream)
 {
-	return classify_v4_ctlb(c, t, hash, n, now, out, rn, stream);
-}
-
-static int classify_v6_ctlb(cgpu_ctx *c, const cgpu_tuples_v6_ct *t, const uint32_t *hash, size_t n,
-			    uint32_t now, const cgpu_ctlb6_out *out, const cgpu_rnat6_out *rn, void *stream)
-{
-	Pinned P;
-	if (int r = pin(c, stream, P))
-		return r;
-	if (!t || !out || (n && (!t->saddr || !t->daddr || !t->sport || !t->dport || !t->proto || !t->l4 ||
-				 !t->flags || !t->len || !t->ep || !out->verdict || !out->ct_ret ||
-				 !out->identity)))
-		return fail(-EINVAL, "null tuple column or output");
-	if (n && (((uintptr_t)t->saddr | (uintptr_t)t->daddr | (uintptr_t)out->daddr) & 15))
-		return fail(-EINVAL, "IPv6 address columns must be 16-byte aligned");
-	if (n > (size_t)INT32_MAX / 2)
-		return fail(-EINVAL, "batch of %zu packets exceeds 2^30 - 1", n);
-	if (!n)
-		return 0;
-	ct_launch a{};
-	a.saddr = t->saddr;
-	a.daddr = t->daddr;
-	a.sport = t->sport;
-	a.dport = t->dport;
-	a.proto = t->proto;
-	a.l4 = t->l4;
-	a.flags = t->flags;
-	a.len = t->len;
-	a.ep = t->ep;
-	a.verdict = out->verdict;
-	a.ct_ret = out->ct_ret;
-	a.identity = out->identity;
-	a.stage = out->stage;
-	a.xdaddr = out->daddr;
-	a.xdport = out->dport;
-	a.hash = hash;
-	a.n = n;
-	a.now = now;
-	if (int r = rnat6_into(a, rn))
-		return r;
-	return ct_classify(c, P.snap(), P.delta, c->ct6, a, stream, true, rn != nullptr);
-}
-
-CGPU_EXPORT int cgpu_classify_v6_ctlb(cgpu_ctx *c, const cgpu_tuples_v6_ct *t, const uint32_t *hash,
-				      size_t n, uint32_t now, const cgpu_ctlb6_out *out, void *stream)
-{
-	return classify_v6_ctlb(c, t, hash, n, now, out, nullptr, stream);
-}
-
-CGPU_EXPORT int cgpu_classify_v6_ctlb_rnat(cgpu_ctx *c, const cgpu_tuples_v6_ct *t, const uint32_t *hash,
-					   size_t n, uint32_t now, const cgpu_ctlb6_out *out,
-					   const cgpu_rnat6_out *rn, void *stream)
-{
-	return classify_v6_ctlb(c, t, hash, n, now, out, rn, stream);
-}
-
-static int classify_v6_ct(cgpu_ctx *c, const cgpu_tuples_v6_ct *t, size_t n, uint32_t now, int32_t *verdict,
-			  uint8_t *ct_ret, uint32_t *identity, uint8_t *stage, uint32_t *tunnel, void *stream,
-			  const cgpu_rnat6_out *rn = nullptr)
-{
-	Pinned P;
-	if (int r = pin(c, stream, P))
-		return r;
-	if (!t || (n && (!t->saddr || !t->daddr || !t->sport || !t->dport || !t->proto || !t->l4 ||
-			 !t->flags || !t->len || !t->ep || !verdict || !ct_ret || !identity)))
-		return fail(-EINVAL, "null tuple column or output");
-	if (n && (((uintptr_t)t->saddr | (uintptr_t)t->daddr) & 15))
-		return fail(-EINVAL, "IPv6 address columns must be 16-byte aligned");
-	if (n > (size_t)INT32_MAX)
-		return fail(-EINVAL, "batch of %zu packets exceeds 2^31 - 1", n);
-	if (!n)
-		return 0;
-	ct_launch a{};
-	a.saddr = t->saddr;
-	a.daddr = t->daddr;
-	a.sport = t->sport;
-	a.dport = t->dport;
-	a.proto = t->proto;
-	a.l4 = t->l4;
-	a.flags = t->flags;
-	a.len = t->len;
-	a.ep = t->ep;
-	a.verdict = verdict;
-	a.ct_ret = ct_ret;
-	a.identity = identity;
-	a.stage = stage;
-	a.n = n;
-	a.now = now;
-	a.tunnel = tunnel;
-	a.tun = &P.tun();
-	if (int r = rnat6_into(a, rn))
-		return r;
-	return ct_classify(c, P.snap(), P.delta, c->ct6, a, stream, false, rn != nullptr);
-}
-
-CGPU_EXPORT int cgpu_classify_v6_ct_rnat(cgpu_ctx *c, const cgpu_tuples_v6_ct *t, size_t n, uint32_t now,
-					 int32_t *verdict, uint8_t *ct_ret, uint32_t *identity,
-					 uint8_t *stage, const cgpu_rnat6_out *rn, void *stream)
-{
-	return classify_v6_ct(c, t, n, now, verdict, ct_ret, identity, stage, nullptr, stream, rn);
+	CtOuts o;
+	CtRnat r;
+	return classify_ct(c, t, hash, n, now, true, ct_outs(out, o), nullptr, ct_rnat(rn, r), stream);
 }
 
 CGPU_EXPORT int cgpu_classify_v6_ct(cgpu_ctx *c, const cgpu_tuples_v6_ct *t, size_t n, uint32_t now,
 				    int32_t *verdict, uint8_t *ct_ret, uint32_t *identity,
 				    uint8_t *stage, void *stream)
 {
-	return classify_v6_ct(c, t, n, now, verdict, ct_ret, identity, stage, nullptr, stream);
+	return classify_ct_plain(c, t, n, now, verdict, ct_ret, identity, stage, nullptr, nullptr, stream);
+}
+
+CGPU_EXPORT int cgpu_classify_v6_ct_rnat(cgpu_ctx *c, const cgpu_tuples_v6_ct *t, size_t n, uint32_t now,
+					 int32_t *verdict, uint8_t *ct_ret, uint32_t *identity,
+					 uint8_t *stage, const cgpu_rnat6_out *rn, void *stream)
+{
+	CtRnat r;
+	return classify_ct_plain(c, t, n, now, verdict, ct_ret, identity, stage, nullptr, ct_rnat(rn, r), stream);
 }
 
 CGPU_EXPORT int cgpu_classify_v6_ct_tun(cgpu_ctx *c, const cgpu_tuples_v6_ct *t, size_t n, uint32_t now,
@@ -7531,7 +7295,23 @@ CGPU_EXPORT int cgpu_classify_v6_ct_tun(cgpu_ctx *c, const cgpu_tuples_v6_ct *t,
 {
 	if (int r = check_tunnel(c, tunnel))
 		return r;
-	return classify_v6_ct(c, t, n, now, verdict, ct_ret, identity, stage, tunnel, stream);
+	return classify_ct_plain(c, t, n, now, verdict, ct_ret, identity, stage, tunnel, nullptr, stream);
+}
+
+CGPU_EXPORT int cgpu_classify_v6_ctlb(cgpu_ctx *c, const cgpu_tuples_v6_ct *t, const uint32_t *hash,
+				      size_t n, uint32_t now, const cgpu_ctlb6_out *out, void *stream)
+{
+	CtOuts o;
+	return classify_ct(c, t, hash, n, now, true, ct_outs(out, o), nullptr, nullptr, stream);
+}
+
+CGPU_EXPORT int cgpu_classify_v6_ctlb_rnat(cgpu_ctx *c, const cgpu_tuples_v6_ct *t, const uint32_t *hash,
+					   size_t n, uint32_t now, const cgpu_ctlb6_out *out,
+					   const cgpu_rnat6_out *rn, void *stream)
+{
+	CtOuts o;
+	CtRnat r;
+	return classify_ct(c, t, hash, n, now, true, ct_outs(out, o), nullptr, ct_rnat(rn, r), stream);
 }
 
 /* ======================================================================= */
@@ -7555,27 +7335,28 @@ enum { MIR_IPC = 1, MIR_POL, MIR_CIDR, MIR_EP, MIR_LB4, MIR_LB6, MIR_LXC, MIR_RE
 
 struct MirOut {
 	std::vector<uint8_t> buf;
+	/* device-side state the mirror does not hold, read before the sections
+	 * are written: every policy entry with its counters (as cgpu_policy_lookup
+	 * reports them), endpoint by endpoint in key order */
+	std::vector<cgpu_policy_entry> ents;
 	void put(const void *p, size_t n)
 	{
 		const uint8_t *b = static_cast<const uint8_t *>(p);
 		buf.insert(buf.end(), b, b + n);
 	}
 	template <typename T> void put(const T &v) { put(&v, sizeof(v)); }
-	size_t section(uint32_t tag, uint32_t rec)
-	{
-		put(tag);
-		put(rec);
-		const size_t at = buf.size();
-		put((uint64_t)0);
-		return at;
-	}
-	void count(size_t at, uint64_t n) { memcpy(&buf[at], &n, 8); }
 };
 
-static void mir_ct(MirOut &o, uint32_t tag, const CtMap &m, uint32_t ksz)
+/* a field of a record (records are packed: any alignment) */
+template <typename T> static T mir_get(const uint8_t *r)
 {
-	const size_t at = o.section(tag, ksz + 56);
-	uint64_t n = 0;
+	T v;
+	memcpy(&v, r, sizeof(v));
+	return v;
+}
+
+static void mir_ct(MirOut &o, const CtMap &m, uint32_t ksz)
+{
 	for (uint32_t h = 0; h <= m.mask && !m.keys.empty(); h++) {
 		if (ctm_tag(m, h) != CT_TAG_LIVE)
 			continue;
@@ -7588,10 +7369,252 @@ static void mir_ct(MirOut &o, uint32_t tag, const CtMap &m, uint32_t ksz)
 			o.put(&t, ksz);
 		}
 		o.put(&m.vals[4u * h], 56);
-		n++;
 	}
-	o.count(at, n);
 }
+
+/* One section kind.  kMir lists them by tag, which is the order a file holds
+ * them in and part of the format; everything save and restore do per kind
+ * comes from this table.  empty / write run under the mirror lock (the
+ * conntrack shadows pulled); apply and undo go through the map calls the agent
+ * uses (the listeners' path), apply as a NOEXIST insert into the empty context. */
+struct MirKind {
+	uint32_t tag, rec;    /* rec: bytes of one record */
+	bool always;          /* written even without a record (the kinds of the first files) */
+	const char *cap_name; /* NULL: no capacity to hold against the record count */
+	uint64_t (*cap)(const cgpu_ctx *c);
+	bool (*empty)(const cgpu_ctx *c);
+	void (*write)(const cgpu_ctx *c, MirOut &o);
+	int (*apply)(cgpu_ctx *c, const uint8_t *r);
+	void (*undo)(cgpu_ctx *c, const uint8_t *r); /* NULL: another kind's undo covers it */
+};
+
+static_assert(sizeof(cgpu_ipcache_key) == 24 && sizeof(cgpu_policy_key) == 8 && sizeof(cgpu_policy_entry) == 24 &&
+		      sizeof(cgpu_cidr_key) == 20 && sizeof(cgpu_endpoint_key) == 20 && sizeof(cgpu_lb4_key) == 8 &&
+		      sizeof(cgpu_lb4_service) == 12 && sizeof(cgpu_lb6_key) == 20 && sizeof(cgpu_lb6_service) == 24 &&
+		      sizeof(cgpu_lxc_info) == 32 && sizeof(cgpu_ct4_tuple) == 14 && sizeof(cgpu_ct6_tuple) == 38 &&
+		      sizeof(cgpu_ct_entry) == 56 && sizeof(cgpu_lb4_reverse_nat) == 6 &&
+		      sizeof(cgpu_lb6_reverse_nat) == 18 && sizeof(cgpu_endpoint_info) == 48,
+	      "the mirror file's records are these structs back to back");
+
+static uint64_t mir_cap_lb(const cgpu_ctx *c) { return c->cfg.lb_max_entries; }
+
+static const MirKind kMir[] = {
+	{MIR_IPC, 32, true, "ipcache_max", [](const cgpu_ctx *c) -> uint64_t { return c->cfg.ipcache_max; },
+	 [](const cgpu_ctx *c) { return c->ipc.empty(); },
+	 [](const cgpu_ctx *c, MirOut &o) {
+		 for (auto &kv : c->ipc) {
+			 o.put(kv.second.raw);
+			 o.put(kv.second.val);
+		 }
+	 },
+	 [](cgpu_ctx *c, const uint8_t *r) {
+		 const auto k = mir_get<cgpu_ipcache_key>(r);
+		 const auto v = mir_get<cgpu_remote_endpoint_info>(r + 24);
+		 return cgpu_ipcache_update(c, &k, &v, CGPU_NOEXIST);
+	 },
+	 [](cgpu_ctx *c, const uint8_t *r) {
+		 const auto k = mir_get<cgpu_ipcache_key>(r);
+		 cgpu_ipcache_delete(c, &k);
+	 }},
+	/* {u32 endpoint, key, entry}; the per-endpoint limit is checked apart */
+	{MIR_POL, 36, true, nullptr, nullptr, [](const cgpu_ctx *c) { return !c->pol_total; },
+	 [](const cgpu_ctx *c, MirOut &o) {
+		 size_t n = 0;
+		 for (uint32_t ep = 0; ep < c->pol.size(); ep++)
+			 for (auto &kv : c->pol[ep]) {
+				 o.put(ep);
+				 o.put(&kv.first, 8);
+				 o.put(o.ents[n++]);
+			 }
+	 },
+	 [](cgpu_ctx *c, const uint8_t *r) {
+		 const auto k = mir_get<cgpu_policy_key>(r + 4);
+		 const auto e = mir_get<cgpu_policy_entry>(r + 12);
+		 return cgpu_policy_update(c, mir_get<uint32_t>(r), &k, &e, CGPU_NOEXIST);
+	 },
+	 [](cgpu_ctx *c, const uint8_t *r) {
+		 const auto k = mir_get<cgpu_policy_key>(r + 4);
+		 cgpu_policy_delete(c, mir_get<uint32_t>(r), &k);
+	 }},
+	/* {u32 which map, key} */
+	{MIR_CIDR, 24, true, nullptr, nullptr,
+	 [](const cgpu_ctx *c) { return c->dyn4.empty() && c->dyn6.empty() && c->fix4.empty() && c->fix6.empty(); },
+	 [](const cgpu_ctx *c, MirOut &o) {
+		 auto cidr = [&](uint32_t which, const void *key, size_t bytes) {
+			 cgpu_cidr_key k{};
+			 memcpy(&k, key, bytes);
+			 o.put(which);
+			 o.put(k);
+		 };
+		 for (auto &kv : c->dyn4)
+			 cidr(CGPU_CIDR_V4_DYN, &kv.second, sizeof(kv.second));
+		 for (auto &kv : c->dyn6)
+			 cidr(CGPU_CIDR_V6_DYN, &kv.second, sizeof(kv.second));
+		 for (auto &x : c->fix4)
+			 cidr(CGPU_CIDR_V4_FIX, x.data(), x.size());
+		 for (auto &x : c->fix6)
+			 cidr(CGPU_CIDR_V6_FIX, x.data(), x.size());
+	 },
+	 [](cgpu_ctx *c, const uint8_t *r) {
+		 const auto k = mir_get<cgpu_cidr_key>(r + 4);
+		 return cgpu_cidr_update(c, (int)mir_get<uint32_t>(r), &k, CGPU_NOEXIST);
+	 },
+	 [](cgpu_ctx *c, const uint8_t *r) {
+		 const auto k = mir_get<cgpu_cidr_key>(r + 4);
+		 cgpu_cidr_delete(c, (int)mir_get<uint32_t>(r), &k);
+	 }},
+	{MIR_EP, 20, true, "endpoints_max", [](const cgpu_ctx *c) -> uint64_t { return c->cfg.endpoints_max; },
+	 [](const cgpu_ctx *c) { return c->lxc.empty(); },
+	 [](const cgpu_ctx *c, MirOut &o) {
+		 for (auto &x : c->lxc)
+			 o.put(x.data(), 20);
+	 },
+	 [](cgpu_ctx *c, const uint8_t *r) {
+		 const auto k = mir_get<cgpu_endpoint_key>(r);
+		 return cgpu_endpoint_update(c, &k, CGPU_NOEXIST);
+	 },
+	 [](cgpu_ctx *c, const uint8_t *r) {
+		 const auto k = mir_get<cgpu_endpoint_key>(r);
+		 cgpu_endpoint_delete(c, &k);
+	 }},
+	{MIR_LB4, 20, true, "lb_max_entries (lb4)", mir_cap_lb, [](const cgpu_ctx *c) { return c->lb.empty(); },
+	 [](const cgpu_ctx *c, MirOut &o) {
+		 for (auto &kv : c->lb) {
+			 o.put(Lb4Tab::unkey(kv.first));
+			 o.put(kv.second);
+		 }
+	 },
+	 [](cgpu_ctx *c, const uint8_t *r) {
+		 const auto k = mir_get<cgpu_lb4_key>(r);
+		 const auto v = mir_get<cgpu_lb4_service>(r + 8);
+		 return cgpu_lb4_update(c, &k, &v, CGPU_NOEXIST);
+	 },
+	 [](cgpu_ctx *c, const uint8_t *r) {
+		 const auto k = mir_get<cgpu_lb4_key>(r);
+		 cgpu_lb4_delete(c, &k);
+	 }},
+	{MIR_LB6, 44, true, "lb_max_entries (lb6)", mir_cap_lb, [](const cgpu_ctx *c) { return c->lb6.empty(); },
+	 [](const cgpu_ctx *c, MirOut &o) {
+		 for (auto &kv : c->lb6) {
+			 o.put(lb6_unkey(kv.first));
+			 o.put(kv.second);
+		 }
+	 },
+	 [](cgpu_ctx *c, const uint8_t *r) {
+		 const auto k = mir_get<cgpu_lb6_key>(r);
+		 const auto v = mir_get<cgpu_lb6_service>(r + 20);
+		 return cgpu_lb6_update(c, &k, &v, CGPU_NOEXIST);
+	 },
+	 [](cgpu_ctx *c, const uint8_t *r) {
+		 const auto k = mir_get<cgpu_lb6_key>(r);
+		 cgpu_lb6_delete(c, &k);
+	 }},
+	/* {u32 endpoint, info} */
+	{MIR_LXC, 36, true, nullptr, nullptr, [](const cgpu_ctx *c) { return c->lxcinfo.empty(); },
+	 [](const cgpu_ctx *c, MirOut &o) {
+		 for (auto &kv : c->lxcinfo) {
+			 o.put(kv.first);
+			 o.put(kv.second);
+		 }
+	 },
+	 [](cgpu_ctx *c, const uint8_t *r) {
+		 const auto v = mir_get<cgpu_lxc_info>(r + 4);
+		 return cgpu_lxc_update(c, mir_get<uint32_t>(r), &v);
+	 },
+	 [](cgpu_ctx *c, const uint8_t *r) { cgpu_lxc_delete(c, mir_get<uint32_t>(r)); }},
+	/* the PreFilter revision: always one record, no part of "empty", and put
+	 * back by mirror_rollback itself, which knows the value it had */
+	{MIR_REV, 8, true, nullptr, nullptr, [](const cgpu_ctx *) { return true; },
+	 [](const cgpu_ctx *c, MirOut &o) { o.put(c->pf_revision); },
+	 [](cgpu_ctx *c, const uint8_t *r) {
+		 std::lock_guard<std::mutex> g(c->mu);
+		 c->pf_revision = mir_get<int64_t>(r);
+		 return 0;
+	 },
+	 nullptr},
+	{MIR_CT4, 70, true, "ct_max", [](const cgpu_ctx *c) -> uint64_t { return c->ct4.max; },
+	 [](const cgpu_ctx *c) { return !c->ct4.live; }, [](const cgpu_ctx *c, MirOut &o) { mir_ct(o, c->ct4, 14); },
+	 [](cgpu_ctx *c, const uint8_t *r) {
+		 const auto k = mir_get<cgpu_ct4_tuple>(r);
+		 const auto v = mir_get<cgpu_ct_entry>(r + 14);
+		 return cgpu_ct4_update(c, &k, &v, CGPU_NOEXIST);
+	 },
+	 [](cgpu_ctx *c, const uint8_t *r) {
+		 const auto k = mir_get<cgpu_ct4_tuple>(r);
+		 cgpu_ct4_delete(c, &k);
+	 }},
+	{MIR_CT6, 94, true, "ct6_max", [](const cgpu_ctx *c) -> uint64_t { return c->ct6.max; },
+	 [](const cgpu_ctx *c) { return !c->ct6.live; }, [](const cgpu_ctx *c, MirOut &o) { mir_ct(o, c->ct6, 38); },
+	 [](cgpu_ctx *c, const uint8_t *r) {
+		 const auto k = mir_get<cgpu_ct6_tuple>(r);
+		 const auto v = mir_get<cgpu_ct_entry>(r + 38);
+		 return cgpu_ct6_update(c, &k, &v, CGPU_NOEXIST);
+	 },
+	 [](cgpu_ctx *c, const uint8_t *r) {
+		 const auto k = mir_get<cgpu_ct6_tuple>(r);
+		 cgpu_ct6_delete(c, &k);
+	 }},
+	/* {u16 index, value}; absent from files written before they existed */
+	{MIR_RN4, 8, true, "lb_max_entries (reverse NAT 4)", mir_cap_lb,
+	 [](const cgpu_ctx *c) { return c->rn4.empty(); },
+	 [](const cgpu_ctx *c, MirOut &o) {
+		 for (auto &kv : c->rn4) {
+			 o.put(kv.first);
+			 o.put(kv.second);
+		 }
+	 },
+	 [](cgpu_ctx *c, const uint8_t *r) {
+		 const auto v = mir_get<cgpu_lb4_reverse_nat>(r + 2);
+		 return cgpu_revnat4_update(c, mir_get<uint16_t>(r), &v, CGPU_NOEXIST);
+	 },
+	 [](cgpu_ctx *c, const uint8_t *r) { cgpu_revnat4_delete(c, mir_get<uint16_t>(r)); }},
+	{MIR_RN6, 20, true, "lb_max_entries (reverse NAT 6)", mir_cap_lb,
+	 [](const cgpu_ctx *c) { return c->rn6.empty(); },
+	 [](const cgpu_ctx *c, MirOut &o) {
+		 for (auto &kv : c->rn6) {
+			 o.put(kv.first);
+			 o.put(kv.second);
+		 }
+	 },
+	 [](cgpu_ctx *c, const uint8_t *r) {
+		 const auto v = mir_get<cgpu_lb6_reverse_nat>(r + 2);
+		 return cgpu_revnat6_update(c, mir_get<uint16_t>(r), &v, CGPU_NOEXIST);
+	 },
+	 [](cgpu_ctx *c, const uint8_t *r) { cgpu_revnat6_delete(c, mir_get<uint16_t>(r)); }},
+	/* {endpoint key, endpoint_info} of the MIR_EP keys whose value is not
+	 * all-zero: set on the key MIR_EP inserted, and deleted with it */
+	{MIR_EPI, 68, false, nullptr, nullptr, [](const cgpu_ctx *c) { return c->lxc_info.empty(); },
+	 [](const cgpu_ctx *c, MirOut &o) {
+		 for (auto &kv : c->lxc_info) {
+			 o.put(kv.first.data(), 20);
+			 o.put(kv.second);
+		 }
+	 },
+	 [](cgpu_ctx *c, const uint8_t *r) {
+		 const auto k = mir_get<cgpu_endpoint_key>(r);
+		 const auto v = mir_get<cgpu_endpoint_info>(r + 20);
+		 return cgpu_endpoint_update_info(c, &k, &v, CGPU_EXIST);
+	 },
+	 nullptr},
+	/* {tunnel key, value} */
+	{MIR_TUN, 40, false, "the tunnel map's size", [](const cgpu_ctx *) -> uint64_t { return CGPU_TUNNEL_MAP_SIZE; },
+	 [](const cgpu_ctx *c) { return c->tun.empty(); },
+	 [](const cgpu_ctx *c, MirOut &o) {
+		 for (auto &kv : c->tun) {
+			 o.put(kv.first.data(), 20);
+			 o.put(kv.second);
+		 }
+	 },
+	 [](cgpu_ctx *c, const uint8_t *r) {
+		 const auto k = mir_get<cgpu_endpoint_key>(r), v = mir_get<cgpu_endpoint_key>(r + 20);
+		 return cgpu_tunnel_update(c, &k, &v, CGPU_NOEXIST);
+	 },
+	 [](cgpu_ctx *c, const uint8_t *r) {
+		 const auto k = mir_get<cgpu_endpoint_key>(r);
+		 cgpu_tunnel_delete(c, &k);
+	 }},
+};
+static_assert(sizeof(kMir) / sizeof(kMir[0]) == MIR_LAST, "one MirKind per tag, kMir[tag - 1]");
 
 CGPU_EXPORT int cgpu_mirror_save(cgpu_ctx *c, const char *path)
 {
@@ -7600,118 +7623,33 @@ CGPU_EXPORT int cgpu_mirror_save(cgpu_ctx *c, const char *path)
 	MirOut o;
 	o.put("CGPUMIR1", 8);
 	o.put((uint32_t)1);
-	o.put((uint32_t)12);
+	uint32_t nsec = 0;
+	o.put(nsec); /* filled in below */
 	{
 		std::lock_guard<std::mutex> g(c->mu);
-		/* device-side state the mirror does not hold: per-entry counters
-		 * (as cgpu_policy_lookup reports them) and the conntrack maps */
 		std::vector<std::pair<const PolEntry *, size_t>> hit;
 		for (uint32_t ep = 0; ep < c->pol.size(); ep++)
 			for (auto &kv : c->pol[ep])
 				hit.push_back({&kv.second, hit.size()});
-		std::vector<cgpu_policy_entry> ents(hit.size());
-		if (int r = policy_fill(c, hit, ents.data()))
+		o.ents.resize(hit.size());
+		if (int r = policy_fill(c, hit, o.ents.data()))
 			return r;
 		if (int r = ct_pull(c, c->ct4))
 			return r;
 		if (int r = ct_pull(c, c->ct6))
 			return r;
-		size_t at = o.section(MIR_IPC, 32);
-		for (auto &kv : c->ipc) {
-			o.put(kv.second.raw);
-			o.put(kv.second.val);
-		}
-		o.count(at, c->ipc.size());
-		at = o.section(MIR_POL, 36);
-		uint64_t n = 0;
-		for (uint32_t ep = 0; ep < c->pol.size(); ep++)
-			for (auto &kv : c->pol[ep]) {
-				o.put(ep);
-				o.put(&kv.first, 8);
-				o.put(ents[n]);
-				n++;
+		for (const MirKind &k : kMir) {
+			const size_t at = o.buf.size();
+			o.put(k.tag);
+			o.put(k.rec);
+			o.put((uint64_t)0);
+			k.write(c, o);
+			const uint64_t n = (o.buf.size() - at - 16) / k.rec;
+			if (!n && !k.always) {
+				o.buf.resize(at); /* a mirror that never used it saves the file it always did */
+				continue;
 			}
-		o.count(at, n);
-		at = o.section(MIR_CIDR, 24);
-		n = 0;
-		auto cidr = [&](uint32_t which, const cgpu_cidr_key &k) {
-			o.put(which);
-			o.put(k);
-			n++;
-		};
-		for (auto &kv : c->dyn4)
-			cidr(CGPU_CIDR_V4_DYN, kv.second);
-		for (auto &kv : c->dyn6)
-			cidr(CGPU_CIDR_V6_DYN, kv.second);
-		for (auto &x : c->fix4) {
-			cgpu_cidr_key k{};
-			memcpy(&k, x.data(), x.size());
-			cidr(CGPU_CIDR_V4_FIX, k);
-		}
-		for (auto &x : c->fix6) {
-			cgpu_cidr_key k{};
-			memcpy(&k, x.data(), x.size());
-			cidr(CGPU_CIDR_V6_FIX, k);
-		}
-		o.count(at, n);
-		at = o.section(MIR_EP, 20);
-		for (auto &x : c->lxc)
-			o.put(x.data(), 20);
-		o.count(at, c->lxc.size());
-		at = o.section(MIR_LB4, 20);
-		for (auto &kv : c->lb) {
-			const cgpu_lb4_key k = lb_unkey(kv.first);
-			o.put(k);
-			o.put(kv.second);
-		}
-		o.count(at, c->lb.size());
-		at = o.section(MIR_LB6, 44);
-		for (auto &kv : c->lb6) {
-			const cgpu_lb6_key k = lb6_unkey(kv.first);
-			o.put(k);
-			o.put(kv.second);
-		}
-		o.count(at, c->lb6.size());
-		at = o.section(MIR_LXC, 36);
-		for (auto &kv : c->lxcinfo) {
-			o.put(kv.first);
-			o.put(kv.second);
-		}
-		o.count(at, c->lxcinfo.size());
-		at = o.section(MIR_REV, 8);
-		o.put(c->pf_revision);
-		o.count(at, 1);
-		mir_ct(o, MIR_CT4, c->ct4, 14);
-		mir_ct(o, MIR_CT6, c->ct6, 38);
-		at = o.section(MIR_RN4, 8);
-		for (auto &kv : c->rn4) {
-			o.put(kv.first);
-			o.put(kv.second);
-		}
-		o.count(at, c->rn4.size());
-		at = o.section(MIR_RN6, 20);
-		for (auto &kv : c->rn6) {
-			o.put(kv.first);
-			o.put(kv.second);
-		}
-		o.count(at, c->rn6.size());
-		uint32_t nsec = 12;
-		if (!c->lxc_info.empty()) {
-			at = o.section(MIR_EPI, 68);
-			for (auto &kv : c->lxc_info) {
-				o.put(kv.first.data(), 20);
-				o.put(kv.second);
-			}
-			o.count(at, c->lxc_info.size());
-			nsec++;
-		}
-		if (!c->tun.empty()) {
-			at = o.section(MIR_TUN, 40);
-			for (auto &kv : c->tun) {
-				o.put(kv.first.data(), 20);
-				o.put(kv.second.data(), 20);
-			}
-			o.count(at, c->tun.size());
+			memcpy(&o.buf[at + 8], &n, 8);
 			nsec++;
 		}
 		memcpy(&o.buf[12], &nsec, 4);
@@ -7730,116 +7668,26 @@ CGPU_EXPORT int cgpu_mirror_save(cgpu_ctx *c, const char *path)
 }
 
 struct MirSec {
-	uint32_t tag, rec;
+	const MirKind *kind;
 	uint64_t n;
 	size_t off;
 };
 
-struct CgpuConfigCaps {
-	uint64_t ipcache, policy_per_ep, endpoints, lb, ct4, ct6;
-};
-
-static CgpuConfigCaps config_caps(const cgpu_ctx *c)
-{
-	return CgpuConfigCaps{c->cfg.ipcache_max, c->cfg.policy_max_per_ep, c->cfg.endpoints_max,
-			      c->cfg.lb_max_entries, c->ct4.max, c->ct6.max};
-}
-
-/* undo a partial replay: delete, newest first, every record of sections
- * [0, si) and records [0, upto) of section si (each was a NOEXIST insert
- * into the empty context), and put the prefilter revision back */
+/* undo a partial replay: newest first, every record of sections [0, si) and
+ * records [0, upto) of section si, and put the prefilter revision back */
 static void mirror_rollback(cgpu_ctx *c, const std::vector<uint8_t> &buf, const std::vector<MirSec> &secs,
 			    size_t si, uint64_t upto, int64_t rev0)
 {
 	for (size_t k = si + 1; k-- > 0;) {
 		const MirSec &s_ = secs[k];
-		const uint64_t n = k == si ? upto : s_.n;
-		for (uint64_t i = n; i-- > 0;) {
-			const uint8_t *r = &buf[s_.off + i * s_.rec];
-			switch (s_.tag) {
-			case MIR_IPC: {
-				cgpu_ipcache_key key;
-				memcpy(&key, r, 24);
-				cgpu_ipcache_delete(c, &key);
-				break;
-			}
-			case MIR_POL: {
-				uint32_t ep;
-				cgpu_policy_key key;
-				memcpy(&ep, r, 4);
-				memcpy(&key, r + 4, 8);
-				cgpu_policy_delete(c, ep, &key);
-				break;
-			}
-			case MIR_CIDR: {
-				uint32_t which;
-				cgpu_cidr_key key;
-				memcpy(&which, r, 4);
-				memcpy(&key, r + 4, 20);
-				cgpu_cidr_delete(c, (int)which, &key);
-				break;
-			}
-			case MIR_EP: {
-				cgpu_endpoint_key key;
-				memcpy(&key, r, 20);
-				cgpu_endpoint_delete(c, &key);
-				break;
-			}
-			case MIR_LB4: {
-				cgpu_lb4_key key;
-				memcpy(&key, r, 8);
-				cgpu_lb4_delete(c, &key);
-				break;
-			}
-			case MIR_LB6: {
-				cgpu_lb6_key key;
-				memcpy(&key, r, 20);
-				cgpu_lb6_delete(c, &key);
-				break;
-			}
-			case MIR_LXC: {
-				uint32_t ep;
-				memcpy(&ep, r, 4);
-				cgpu_lxc_delete(c, ep);
-				break;
-			}
-			case MIR_REV: {
-				std::lock_guard<std::mutex> g(c->mu);
-				c->pf_revision = rev0;
-				break;
-			}
-			case MIR_CT4: {
-				cgpu_ct4_tuple key;
-				memcpy(&key, r, 14);
-				cgpu_ct4_delete(c, &key);
-				break;
-			}
-			case MIR_CT6: {
-				cgpu_ct6_tuple key;
-				memcpy(&key, r, 38);
-				cgpu_ct6_delete(c, &key);
-				break;
-			}
-			case MIR_RN4:
-			case MIR_RN6: {
-				uint16_t index;
-				memcpy(&index, r, 2);
-				if (s_.tag == MIR_RN4)
-					cgpu_revnat4_delete(c, index);
-				else
-					cgpu_revnat6_delete(c, index);
-				break;
-			}
-			case MIR_EPI: /* its key is a MIR_EP record: deleted there, value and all */
-				break;
-			case MIR_TUN: {
-				cgpu_endpoint_key key;
-				memcpy(&key, r, 20);
-				cgpu_tunnel_delete(c, &key);
-				break;
-			}
-			}
+		if (s_.kind->tag == MIR_REV) {
+			std::lock_guard<std::mutex> g(c->mu);
+			c->pf_revision = rev0;
 		}
+		if (!s_.kind->undo)
+			continue;
+		for (uint64_t i = k == si ? upto : s_.n; i-- > 0;)
+			s_.kind->undo(c, &buf[s_.off + i * s_.kind->rec]);
 	}
 }
 
@@ -7860,46 +7708,35 @@ CGPU_EXPORT int cgpu_mirror_restore(cgpu_ctx *c, const char *path)
 	}
 	if (buf.size() < 24 || memcmp(buf.data(), "CGPUMIR1", 8))
 		return fail(-EINVAL, "%s is not a cgpu mirror snapshot", path);
-	uint64_t want;
-	memcpy(&want, &buf[buf.size() - 8], 8);
-	if (fnv(1469598103934665603ull, buf.data(), buf.size() - 8) != want)
+	if (fnv(1469598103934665603ull, buf.data(), buf.size() - 8) != mir_get<uint64_t>(&buf[buf.size() - 8]))
 		return fail(-EINVAL, "%s: checksum mismatch (truncated or corrupted)", path);
-	uint32_t version, nsec;
-	memcpy(&version, &buf[8], 4);
-	memcpy(&nsec, &buf[12], 4);
+	const uint32_t version = mir_get<uint32_t>(&buf[8]), nsec = mir_get<uint32_t>(&buf[12]);
 	if (version != 1)
 		return fail(-EINVAL, "%s: snapshot version %u", path, version);
+	int64_t rev0;
 	{
 		std::lock_guard<std::mutex> g(c->mu);
-		bool empty = c->ipc.empty() && !c->pol_total && c->dyn4.empty() && c->dyn6.empty() &&
-			     c->fix4.empty() && c->fix6.empty() && c->lxc.empty() && c->lb.empty() &&
-			     c->lb6.empty() && c->lxcinfo.empty() && c->rn4.empty() && c->rn6.empty() && c->tun.empty();
-		for (CtMap *m : {&c->ct4, &c->ct6}) {
+		for (CtMap *m : {&c->ct4, &c->ct6})
 			if (int r = ct_pull(c, *m))
 				return r;
-			empty = empty && !m->live;
-		}
-		if (!empty)
-			return fail(-EEXIST, "restore needs an empty context");
+		for (const MirKind &k : kMir)
+			if (!k.empty(c))
+				return fail(-EEXIST, "restore needs an empty context");
+		rev0 = c->pf_revision;
 	}
 	/* validate the section structure before applying anything */
-	typedef MirSec Sec;
-	std::vector<Sec> secs;
+	std::vector<MirSec> secs;
 	size_t off = 16;
 	const size_t end = buf.size() - 8;
-	static const uint32_t recsz[] = {0, 32, 36, 24, 20, 20, 44, 36, 8, 70, 94, 8, 20, 68, 40};
 	for (uint32_t i = 0; i < nsec; i++) {
-		Sec s_;
 		if (off + 16 > end)
 			return fail(-EINVAL, "%s: truncated section header", path);
-		memcpy(&s_.tag, &buf[off], 4);
-		memcpy(&s_.rec, &buf[off + 4], 4);
-		memcpy(&s_.n, &buf[off + 8], 8);
-		s_.off = off + 16;
-		if (s_.tag < MIR_IPC || s_.tag > MIR_LAST || s_.rec != recsz[s_.tag] ||
-		    s_.n > (end - s_.off) / s_.rec)
-			return fail(-EINVAL, "%s: bad section %u", path, s_.tag);
-		off = s_.off + s_.n * s_.rec;
+		const uint32_t tag = mir_get<uint32_t>(&buf[off]);
+		MirSec s_{tag >= MIR_IPC && tag <= MIR_LAST ? &kMir[tag - 1] : nullptr, mir_get<uint64_t>(&buf[off + 8]),
+			  off + 16};
+		if (!s_.kind || mir_get<uint32_t>(&buf[off + 4]) != s_.kind->rec || s_.n > (end - s_.off) / s_.kind->rec)
+			return fail(-EINVAL, "%s: bad section %u", path, tag);
+		off = s_.off + s_.n * s_.kind->rec;
 		secs.push_back(s_);
 	}
 	if (off != end)
@@ -7910,165 +7747,31 @@ CGPU_EXPORT int cgpu_mirror_restore(cgpu_ctx *c, const char *path)
 	{
 		uint64_t cnt[MIR_LAST + 1] = {};
 		std::map<uint32_t, uint64_t> per_ep;
-		for (const Sec &s_ : secs) {
-			cnt[s_.tag] += s_.n;
-			if (s_.tag == MIR_POL)
-				for (uint64_t i = 0; i < s_.n; i++) {
-					uint32_t ep;
-					memcpy(&ep, &buf[s_.off + i * s_.rec], 4);
-					per_ep[ep]++;
-				}
+		for (const MirSec &s_ : secs) {
+			cnt[s_.kind->tag] += s_.n;
+			if (s_.kind->tag == MIR_POL)
+				for (uint64_t i = 0; i < s_.n; i++)
+					per_ep[mir_get<uint32_t>(&buf[s_.off + i * s_.kind->rec])]++;
 		}
-		const CgpuConfigCaps cap = config_caps(c);
-		const struct {
-			int tag;
-			uint64_t max;
-			const char *what;
-		} lim[] = {{MIR_IPC, cap.ipcache, "ipcache_max"},   {MIR_EP, cap.endpoints, "endpoints_max"},
-			   {MIR_LB4, cap.lb, "lb_max_entries (lb4)"}, {MIR_LB6, cap.lb, "lb_max_entries (lb6)"},
-			   {MIR_CT4, cap.ct4, "ct_max"},              {MIR_CT6, cap.ct6, "ct6_max"},
-			   {MIR_RN4, cap.lb, "lb_max_entries (reverse NAT 4)"},
-			   {MIR_RN6, cap.lb, "lb_max_entries (reverse NAT 6)"},
-			   {MIR_TUN, CGPU_TUNNEL_MAP_SIZE, "the tunnel map's size"}};
-		for (const auto &l : lim)
-			if (cnt[l.tag] > l.max)
+		for (const MirKind &k : kMir)
+			if (k.cap_name && cnt[k.tag] > k.cap(c))
 				return fail(-E2BIG, "%s: %llu records exceed this context's %s (%llu)", path,
-					    (unsigned long long)cnt[l.tag], l.what, (unsigned long long)l.max);
+					    (unsigned long long)cnt[k.tag], k.cap_name, (unsigned long long)k.cap(c));
 		for (const auto &kv : per_ep)
-			if (kv.second > cap.policy_per_ep)
+			if (kv.second > c->cfg.policy_max_per_ep)
 				return fail(-E2BIG, "%s: %llu policy keys of endpoint %u exceed policy_max_per_ep (%llu)",
 					    path, (unsigned long long)kv.second, kv.first,
-					    (unsigned long long)cap.policy_per_ep);
+					    (unsigned long long)c->cfg.policy_max_per_ep);
 	}
-	/* replay through the map calls (the listeners' path); a record that
-	 * still fails (a per-family limit, a bad key) rolls every applied record
-	 * back, so the context is empty again and the restore can be retried */
-	int64_t rev0;
-	{
-		std::lock_guard<std::mutex> g(c->mu);
-		rev0 = c->pf_revision;
-	}
-	for (size_t si = 0; si < secs.size(); si++) {
-		const Sec &s_ = secs[si];
-		for (uint64_t i = 0; i < s_.n; i++) {
-			const uint8_t *r = &buf[s_.off + i * s_.rec];
-			int rc = 0;
-			switch (s_.tag) {
-			case MIR_IPC: {
-				cgpu_ipcache_key k;
-				cgpu_remote_endpoint_info v;
-				memcpy(&k, r, 24);
-				memcpy(&v, r + 24, 8);
-				rc = cgpu_ipcache_update(c, &k, &v, CGPU_NOEXIST);
-				break;
-			}
-			case MIR_POL: {
-				uint32_t ep;
-				cgpu_policy_key k;
-				cgpu_policy_entry e;
-				memcpy(&ep, r, 4);
-				memcpy(&k, r + 4, 8);
-				memcpy(&e, r + 12, 24);
-				rc = cgpu_policy_update(c, ep, &k, &e, CGPU_NOEXIST);
-				break;
-			}
-			case MIR_CIDR: {
-				uint32_t which;
-				cgpu_cidr_key k;
-				memcpy(&which, r, 4);
-				memcpy(&k, r + 4, 20);
-				rc = cgpu_cidr_update(c, (int)which, &k, CGPU_NOEXIST);
-				break;
-			}
-			case MIR_EP: {
-				cgpu_endpoint_key k;
-				memcpy(&k, r, 20);
-				rc = cgpu_endpoint_update(c, &k, CGPU_NOEXIST);
-				break;
-			}
-			case MIR_LB4: {
-				cgpu_lb4_key k;
-				cgpu_lb4_service v;
-				memcpy(&k, r, 8);
-				memcpy(&v, r + 8, 12);
-				rc = cgpu_lb4_update(c, &k, &v, CGPU_NOEXIST);
-				break;
-			}
-			case MIR_LB6: {
-				cgpu_lb6_key k;
-				cgpu_lb6_service v;
-				memcpy(&k, r, 20);
-				memcpy(&v, r + 20, 24);
-				rc = cgpu_lb6_update(c, &k, &v, CGPU_NOEXIST);
-				break;
-			}
-			case MIR_LXC: {
-				uint32_t ep;
-				cgpu_lxc_info v;
-				memcpy(&ep, r, 4);
-				memcpy(&v, r + 4, 32);
-				rc = cgpu_lxc_update(c, ep, &v);
-				break;
-			}
-			case MIR_REV: {
-				std::lock_guard<std::mutex> g(c->mu);
-				memcpy(&c->pf_revision, r, 8);
-				break;
-			}
-			case MIR_CT4: {
-				cgpu_ct4_tuple k;
-				cgpu_ct_entry v;
-				memcpy(&k, r, 14);
-				memcpy(&v, r + 14, 56);
-				rc = cgpu_ct4_update(c, &k, &v, CGPU_NOEXIST);
-				break;
-			}
-			case MIR_CT6: {
-				cgpu_ct6_tuple k;
-				cgpu_ct_entry v;
-				memcpy(&k, r, 38);
-				memcpy(&v, r + 38, 56);
-				rc = cgpu_ct6_update(c, &k, &v, CGPU_NOEXIST);
-				break;
-			}
-			case MIR_RN4: {
-				uint16_t index;
-				cgpu_lb4_reverse_nat v;
-				memcpy(&index, r, 2);
-				memcpy(&v, r + 2, 6);
-				rc = cgpu_revnat4_update(c, index, &v, CGPU_NOEXIST);
-				break;
-			}
-			case MIR_RN6: {
-				uint16_t index;
-				cgpu_lb6_reverse_nat v;
-				memcpy(&index, r, 2);
-				memcpy(&v, r + 2, 18);
-				rc = cgpu_revnat6_update(c, index, &v, CGPU_NOEXIST);
-				break;
-			}
-			case MIR_EPI: {
-				cgpu_endpoint_key k;
-				cgpu_endpoint_info v;
-				memcpy(&k, r, 20);
-				memcpy(&v, r + 20, 48);
-				rc = cgpu_endpoint_update_info(c, &k, &v, CGPU_EXIST);
-				break;
-			}
-			case MIR_TUN: {
-				cgpu_endpoint_key k, v;
-				memcpy(&k, r, 20);
-				memcpy(&v, r + 20, 20);
-				rc = cgpu_tunnel_update(c, &k, &v, CGPU_NOEXIST);
-				break;
-			}
-			}
-			if (rc) {
+	/* replay; a record that still fails (a per-family limit, a bad key) rolls
+	 * every applied record back, so the context is empty again and the
+	 * restore can be retried */
+	for (size_t si = 0; si < secs.size(); si++)
+		for (uint64_t i = 0; i < secs[si].n; i++)
+			if (int rc = secs[si].kind->apply(c, &buf[secs[si].off + i * secs[si].kind->rec])) {
 				mirror_rollback(c, buf, secs, si, i, rev0);
 				return rc;
 			}
-		}
-	}
 	return 0;
 }
 

@@ -88,6 +88,41 @@ static void tables(cgpu_ctx *c, std::mt19937 &rng, int rounds)
 		ek.family = 1 + (rng() & 1);
 		ek.ip[15] = (uint8_t)rng();
 		(void)cgpu_endpoint_update(c, &ek, 0);
+		cgpu_endpoint_info ei{};
+		ei.ifindex = (uint32_t)(rng() % 3); /* one in three is the all-zero value */
+		ei.mac = ei.ifindex ? 0x5f4e3d2c1b0aull : 0;
+		ek.ip[15] = (uint8_t)rng();
+		const int er = cgpu_endpoint_update_info(c, &ek, &ei, rng() % 3);
+		CHECK(er == 0 || er == -EEXIST || er == -ENOENT || er == -E2BIG);
+		(void)cgpu_endpoint_lookup_info(c, &ek, &ei);
+		if (rng() % 5 == 0)
+			(void)cgpu_endpoint_delete(c, &ek);
+
+		cgpu_endpoint_key tk{}, tv{};
+		tk.family = 1 + (rng() & 1);
+		tk.ip[2] = (uint8_t)(rng() % 48);
+		tv.family = 1;
+		tv.ip[3] = (uint8_t)rng();
+		const int tr = cgpu_tunnel_update(c, &tk, &tv, rng() % 4); /* flag 3: -EINVAL */
+		CHECK(tr == 0 || tr == -EEXIST || tr == -ENOENT || tr == -EINVAL);
+		(void)cgpu_tunnel_lookup(c, &tk, &tv);
+		if (rng() % 4 == 0)
+			(void)cgpu_tunnel_delete(c, &tk);
+
+		const uint16_t ri = (uint16_t)(rng() % 96);
+		cgpu_lb4_reverse_nat n4{(uint32_t)rng(), (uint16_t)rng()};
+		cgpu_lb6_reverse_nat n6{};
+		n6.address[15] = (uint8_t)rng();
+		const int nr = cgpu_revnat4_update(c, ri, &n4, rng() % 3);
+		CHECK(nr == 0 || nr == -EEXIST || nr == -ENOENT);
+		const int nr6 = cgpu_revnat6_update(c, ri, &n6, rng() % 3);
+		CHECK(nr6 == 0 || nr6 == -EEXIST || nr6 == -ENOENT);
+		(void)cgpu_revnat4_lookup(c, (uint16_t)(ri + 1), &n4);
+		(void)cgpu_revnat6_lookup(c, (uint16_t)(ri + 1), &n6);
+		if (rng() % 4 == 0) {
+			(void)cgpu_revnat4_delete(c, ri);
+			(void)cgpu_revnat6_delete(c, (uint16_t)(ri ^ 1));
+		}
 
 		cgpu_lb4_key lk{(uint32_t)rng() % 64, (uint16_t)(rng() % 3), (uint16_t)(rng() % 4)};
 		cgpu_lb4_service ls{(uint32_t)rng(), 80, (uint16_t)(rng() % 4), 1, 0};
@@ -98,8 +133,24 @@ static void tables(cgpu_ctx *c, std::mt19937 &rng, int rounds)
 		cgpu_lb6_service s6{};
 		s6.count = 2;
 		(void)cgpu_lb6_update(c, &l6, &s6, 0);
-		if (rng() % 7 == 0)
+		if (rng() % 7 == 0) {
 			(void)cgpu_lb4_delete(c, &lk);
+			(void)cgpu_lb6_delete(c, &l6);
+		}
+		if (rng() % 31 == 0) {
+			cgpu_lb4_key bk[3] = {lk, lk, lk};
+			cgpu_lb4_service bs[3] = {ls, ls, ls};
+			bk[1].slave = 5;
+			bk[2].slave = 6;
+			const int br = cgpu_lb4_update_batch(c, bk, bs, 3, rng() % 3);
+			CHECK(br == 0 || br == -EEXIST || br == -ENOENT || br == -E2BIG);
+			cgpu_lb6_key b6[2] = {l6, l6};
+			cgpu_lb6_service v6[2] = {s6, s6};
+			b6[1].slave = 7;
+			const int br6 = cgpu_lb6_update_batch(c, b6, v6, 2, 0);
+			CHECK(br6 == 0 || br6 == -E2BIG);
+		}
+		(void)cgpu_lb6_lookup(c, &l6, &s6);
 
 		cgpu_lxc_info li{};
 		li.sec_label = (uint32_t)rng();
@@ -169,6 +220,30 @@ static void walks(cgpu_ctx *c)
 		l4 = m4;
 		r4 = &l4;
 	}
+	cgpu_lb6_key l6, m6;
+	const cgpu_lb6_key *r6 = nullptr;
+	while (cgpu_lb6_get_next_key(c, r6, &m6) == 0) {
+		l6 = m6;
+		r6 = &l6;
+	}
+	cgpu_endpoint_key tk, tn;
+	const cgpu_endpoint_key *tp = nullptr;
+	while (cgpu_tunnel_get_next_key(c, tp, &tn) == 0) {
+		tk = tn;
+		tp = &tk;
+	}
+	uint16_t ri, rn;
+	const uint16_t *rp = nullptr;
+	while (cgpu_revnat4_get_next_key(c, rp, &rn) == 0) {
+		ri = rn;
+		rp = &ri;
+	}
+	rp = nullptr;
+	while (cgpu_revnat6_get_next_key(c, rp, &rn) == 0) {
+		ri = rn;
+		rp = &ri;
+	}
+	(void)cgpu_lb4_count(c);
 	(void)cgpu_ipcache_count(c);
 	(void)cgpu_ct4_count(c);
 	(void)cgpu_ct6_count(c);
@@ -203,6 +278,10 @@ static void checkpoint(cgpu_ctx *c, const std::string &dir)
 	CHECK(cgpu_ipcache_count(d) == cgpu_ipcache_count(c));
 	CHECK(cgpu_ct4_count(d) == cgpu_ct4_count(c));
 	CHECK(cgpu_ct6_count(d) == cgpu_ct6_count(c));
+	CHECK(cgpu_lb4_count(d) == cgpu_lb4_count(c) && cgpu_lb6_count(d) == cgpu_lb6_count(c));
+	CHECK(cgpu_tunnel_count(d) == cgpu_tunnel_count(c) && cgpu_tunnel_count(c) > 0);
+	CHECK(cgpu_revnat4_count(d) == cgpu_revnat4_count(c) && cgpu_revnat4_count(c) > 0);
+	CHECK(cgpu_revnat6_count(d) == cgpu_revnat6_count(c) && cgpu_revnat6_count(c) > 0);
 	CHECK(cgpu_mirror_restore(d, path.c_str()) == -EEXIST);
 	cgpu_ctx_destroy(d);
 	/* a corrupted copy is rejected whole */

@@ -482,6 +482,35 @@ def test_host_batch_entry_errors():
                                      None) == -errno.EINVAL
     assert L_.cgpu_prefilter_v6_host(e.h, a16.ctypes.data, a16.ctypes.data, None, 0, pv.ctypes.data,
                                      None) == -errno.ENODEV
+    # the stateful entry points look at the context first: host-only is
+    # -ENODEV whatever else is wrong (null columns and outputs, a misaligned
+    # IPv6 column, a batch over the limit, an empty batch), no context -EINVAL
+    from cilium_amd._abi import CtlbOut, Rnat4Out, Rnat6Out, TuplesV6Ct
+    no_dev = b"context has no device (host-only); no CPU classification path"
+    tc4, tc6 = TuplesV4Ct(), TuplesV6Ct()
+    tc6.saddr = tc6.daddr = 8
+    out, out6 = CtlbOut(), CtlbOut()
+    out6.daddr = 4
+    rn4, rn6 = Rnat4Out(), Rnat6Out()
+    rn6.saddr = 2
+    nul = [None] * 4
+    for h, want, msg in ((e.h, -errno.ENODEV, no_dev), (None, -errno.EINVAL, b"null context")):
+        for nn in (0, 1, 1 << 31):
+            calls = []
+            for fam, t, o, rn in (("v4", tc4, out, rn4), ("v6", tc6, out6, rn6)):
+                ct, ctlb = f"cgpu_classify_{fam}_ct", f"cgpu_classify_{fam}_ctlb"
+                calls += [(ct, (C.byref(t), nn, 0, *nul, None)), (ct, (None, nn, 0, *nul, None)),
+                          (ct + "_tun", (C.byref(t), nn, 0, *nul, None, None)),
+                          (ct + "_tun", (C.byref(t), nn, 0, *nul, 2, None)),
+                          (ct + "_rnat", (C.byref(t), nn, 0, *nul, C.byref(rn), None)),
+                          (ct + "_rnat", (C.byref(t), nn, 0, *nul, None, None)),
+                          (ctlb, (C.byref(t), None, nn, 0, C.byref(o), None)),
+                          (ctlb, (None, None, nn, 0, None, None)),
+                          (ctlb + "_rnat", (C.byref(t), None, nn, 0, C.byref(o), C.byref(rn), None)),
+                          (ctlb + "_rnat", (C.byref(t), None, nn, 0, None, None, None))]
+            for fn, args in calls:
+                assert getattr(L_, fn)(h, *args) == want, (fn, nn)
+                assert L_.cgpu_last_error() == msg, (fn, nn)
     e.close()
 
 
