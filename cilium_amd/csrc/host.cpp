@@ -939,12 +939,16 @@ uint32_t h64_home(const std::array<uint32_t, 8> &r) { return mix32(r[0], r[1]); 
  * within POL_HOP slots of the home slot, the table doubled until every row
  * fits.  Word T of a slot becomes USED plus, in its top byte, the hop bits of
  * the rows whose home it is (whatever `rows` holds there is dropped); at
- * (optional): the slot each row landed in. */
+ * (optional): the slot each row landed in; doublings (optional): how often
+ * the table doubled (cgpu_diag_hop_tables). */
 template <size_t W, size_t T, uint32_t USED, class H>
 void hop_place(const std::vector<std::array<uint32_t, W>> &rows, H home_of,
-	       std::vector<std::array<uint32_t, W>> &tab, uint32_t &mask, std::vector<uint32_t> *at = nullptr)
+	       std::vector<std::array<uint32_t, W>> &tab, uint32_t &mask, std::vector<uint32_t> *at = nullptr,
+	       uint32_t *doublings = nullptr)
 {
 	uint32_t nb = next_pow2(std::max<uint64_t>(64, 2 * rows.size()));
+	if (doublings)
+		*doublings = 0;
 	for (;; nb *= 2) {
 		tab.assign(nb, std::array<uint32_t, W>{});
 		mask = nb - 1;
@@ -970,6 +974,8 @@ void hop_place(const std::vector<std::array<uint32_t, W>> &rows, H home_of,
 		}
 		if (ok)
 			return;
+		if (doublings)
+			++*doublings;
 	}
 }
 
@@ -1634,6 +1640,10 @@ struct LbBuild {
 	std::vector<std::array<uint32_t, 4>> fe, be;
 	std::vector<uint32_t> vip; /* tables.h lb_table.vip */
 	uint32_t mask = 0, vip_mask = 0;
+	/* of the table as built (cgpu_diag_hop_tables), counted only: frontends
+	 * moved by the hopscotch insertion, and how often the table doubled */
+	uint64_t relocations = 0;
+	uint32_t doublings = 0;
 };
 
 typedef std::vector<std::pair<uint64_t, cgpu_lb4_service>> LbIn; /* sorted by mkey */
@@ -1685,6 +1695,7 @@ int build_lb(const LbIn &lb, uint32_t lb_max_entries, LbBuild &b)
 	for (;;) {
 		b.fe.assign(nb, std::array<uint32_t, 4>{0, 0, 0, 0});
 		b.mask = nb - 1;
+		b.relocations = 0;
 		bool ok = true;
 		auto used = [&](uint32_t i) { return (b.fe[i & b.mask][3] & LB_FE_USED) != 0u; };
 		for (auto &f : fes) {
@@ -1711,6 +1722,7 @@ int build_lb(const LbIn &lb, uint32_t lb_max_entries, LbBuild &b)
 						src[3] &= 0xFF000000u;
 						b.fe[h2][3] = (b.fe[h2][3] & ~(1u << (POL_HOP_SHIFT + o))) | (1u << (POL_HOP_SHIFT + j));
 						d -= j - o;
+						b.relocations++;
 						moved = true;
 						break;
 					}
@@ -1731,6 +1743,7 @@ int build_lb(const LbIn &lb, uint32_t lb_max_entries, LbBuild &b)
 		if (ok)
 			break;
 		nb *= 2;
+		b.doublings++;
 	}
 	if (b.be.empty())
 		b.be.push_back({0, 0, 0, 0});
@@ -1772,6 +1785,7 @@ struct Lb6Build {
 	std::vector<std::array<uint32_t, 8>> fe, be;
 	std::vector<uint32_t> vip;
 	uint32_t mask = 0, vip_mask = 0;
+	uint32_t doublings = 0; /* counted only (cgpu_diag_hop_tables) */
 };
 
 /* cilium_lb6_services -> frontend hash + dense backend rows (tables.h
@@ -1851,6 +1865,7 @@ int build_lb6(const Lb6In &lb, uint32_t lb_max_entries, Lb6Build &b)
 		if (ok)
 			break;
 		nb *= 2;
+		b.doublings++;
 	}
 	if (b.be.empty())
 		b.be.push_back(std::array<uint32_t, 8>{});
@@ -4189,18 +4204,22 @@ static int commit_lxc(cgpu_ctx *c, CommitIn &in, cgpu_snapshot &s, DevBufP &buf)
 	return 0;
 }
 
-/* the forwarding tables (tables.h fwd_tables) from every endpoint with its
- * value and the tunnel map; nothing to build: the snapshot has none */
-static int commit_fwd(cgpu_ctx *c, CommitIn &in, Epoch &e)
+/* the forwarding tables (tables.h fwd_tables, fwd_macs) as host images */
+struct FwdBuild {
+	std::vector<std::array<uint32_t, 4>> e4, t4;
+	std::vector<std::array<uint32_t, 8>> e6, t6;
+	std::vector<std::array<uint8_t, 16>> m4, m6; /* per slot of e4 / row of e6 */
+	uint32_t e4_mask = 0, e6_mask = 0, t4_mask = 0, t6_mask = 0;
+	uint32_t e4_doublings = 0, e6_doublings = 0, t4_doublings = 0, t6_doublings = 0; /* counted only */
+	uint64_t sum = 0;
+};
+
+/* ... built from every endpoint with its value and the tunnel map, in the
+ * maps' order (commit_fwd uploads them; cgpu_diag_hop_tables reads them) */
+static void build_fwd(const CommitIn &in, FwdBuild &f)
 {
-	e.fwdbuf.reset();
-	e.fwd = fwd_tables{};
-	e.fwdm = fwd_macs{};
-	c->b.sum_fwd = 0;
-	if (in.fwd_ep.empty() && in.fwd_tun.empty())
-		return 0;
-	std::vector<std::array<uint32_t, 4>> r4, t4, o_e4, o_t4;
-	std::vector<std::array<uint32_t, 8>> r6, t6, o_e6, o_t6;
+	std::vector<std::array<uint32_t, 4>> r4, t4;
+	std::vector<std::array<uint32_t, 8>> r6, t6;
 	/* per row of r4 / r6: mac's and node_mac's first six bytes as stored, and
 	 * the slot the row lands in */
 	std::vector<std::array<uint8_t, 16>> mac4, mac6;
@@ -4243,24 +4262,45 @@ static int commit_fwd(cgpu_ctx *c, CommitIn &in, Epoch &e)
 		else if (fam == 2 && !w[3])
 			t6.push_back({w[0], w[1], w[2], ip4, 0, 0, 0, 0});
 	}
-	fwd_tables f{};
-	hop_place<4, 3, FWD_USED>(r4, [](const std::array<uint32_t, 4> &r) { return fwd_hash4(r[0]); }, o_e4, f.e4_mask, &at4);
-	hop_place<4, 3, FWD_USED>(t4, [](const std::array<uint32_t, 4> &r) { return fwd_hash4(r[0]); }, o_t4, f.t4_mask);
-	hop_place<8, 6, FWD_USED>(r6, [](const std::array<uint32_t, 8> &r) { return fold6(r[0], r[1], r[2], r[3]); }, o_e6,
-			f.e6_mask, &at6);
-	hop_place<8, 6, FWD_USED>(t6, [](const std::array<uint32_t, 8> &r) { return fold6(r[0], r[1], r[2], 0u); }, o_t6,
-			f.t6_mask);
+	hop_place<4, 3, FWD_USED>(r4, [](const std::array<uint32_t, 4> &r) { return fwd_hash4(r[0]); }, f.e4, f.e4_mask, &at4,
+				  &f.e4_doublings);
+	hop_place<4, 3, FWD_USED>(t4, [](const std::array<uint32_t, 4> &r) { return fwd_hash4(r[0]); }, f.t4, f.t4_mask,
+				  nullptr, &f.t4_doublings);
+	hop_place<8, 6, FWD_USED>(r6, [](const std::array<uint32_t, 8> &r) { return fold6(r[0], r[1], r[2], r[3]); }, f.e6,
+				  f.e6_mask, &at6, &f.e6_doublings);
+	hop_place<8, 6, FWD_USED>(t6, [](const std::array<uint32_t, 8> &r) { return fold6(r[0], r[1], r[2], 0u); }, f.t6,
+				  f.t6_mask, nullptr, &f.t6_doublings);
 	/* the endpoints' MACs at the slot / row their key landed in (fwd_macs) */
-	std::vector<std::array<uint8_t, 16>> m4(o_e4.size(), std::array<uint8_t, 16>{}),
-		m6(o_e6.size(), std::array<uint8_t, 16>{});
+	f.m4.assign(f.e4.size(), std::array<uint8_t, 16>{});
+	f.m6.assign(f.e6.size(), std::array<uint8_t, 16>{});
 	for (size_t i = 0; i < r4.size(); i++)
-		m4[at4[i]] = mac4[i];
+		f.m4[at4[i]] = mac4[i];
 	for (size_t i = 0; i < r6.size(); i++)
-		m6[at6[i]] = mac6[i];
+		f.m6[at6[i]] = mac6[i];
+	f.sum = sum;
+}
+
+/* the forwarding tables of the snapshot; nothing to build: the snapshot has
+ * none */
+static int commit_fwd(cgpu_ctx *c, CommitIn &in, Epoch &e)
+{
+	e.fwdbuf.reset();
+	e.fwd = fwd_tables{};
+	e.fwdm = fwd_macs{};
+	c->b.sum_fwd = 0;
+	if (in.fwd_ep.empty() && in.fwd_tun.empty())
+		return 0;
+	FwdBuild b;
+	build_fwd(in, b);
+	fwd_tables f{};
+	f.e4_mask = b.e4_mask;
+	f.e6_mask = b.e6_mask;
+	f.t4_mask = b.t4_mask;
+	f.t6_mask = b.t6_mask;
 	Arena ar;
-	const size_t a_e4 = ar.add(o_e4.data(), o_e4.size() * 16), a_e6 = ar.add(o_e6.data(), o_e6.size() * 32);
-	const size_t a_m4 = ar.add(m4.data(), m4.size() * 16), a_m6 = ar.add(m6.data(), m6.size() * 16);
-	const size_t a_t4 = ar.add(o_t4.data(), o_t4.size() * 16), a_t6 = ar.add(o_t6.data(), o_t6.size() * 32);
+	const size_t a_e4 = ar.add(b.e4.data(), b.e4.size() * 16), a_e6 = ar.add(b.e6.data(), b.e6.size() * 32);
+	const size_t a_m4 = ar.add(b.m4.data(), b.m4.size() * 16), a_m6 = ar.add(b.m6.data(), b.m6.size() * 16);
+	const size_t a_t4 = ar.add(b.t4.data(), b.t4.size() * 16), a_t6 = ar.add(b.t6.data(), b.t6.size() * 32);
 	if (int r = upload(c, ar, e.fwdbuf, G_N)) /* G_N: summed into the scratch word, not a verified group */
 		return r;
 	f.e4 = at<uint4>(e.fwdbuf, a_e4);
@@ -4269,7 +4309,7 @@ static int commit_fwd(cgpu_ctx *c, CommitIn &in, Epoch &e)
 	f.t6 = at<uint4>(e.fwdbuf, a_t6);
 	e.fwd = f;
 	e.fwdm = fwd_macs{at<uint4>(e.fwdbuf, a_m4), at<uint4>(e.fwdbuf, a_m6)};
-	c->b.sum_fwd = sum;
+	c->b.sum_fwd = b.sum;
 	return 0;
 }
 
@@ -4970,6 +5010,123 @@ CGPU_EXPORT int cgpu_diag_pol_tables(const uint32_t *eps, const cgpu_policy_key 
 	stats[7] = b.pg.count;
 	cgpu_ctx_destroy(c);
 	return rc;
+}
+
+/* Test hook (no header): the service frontend tables (tables.h lb_table.fe,
+ * lb6_table.fe) and the forwarding tables (fwd_tables, fwd_macs) built as
+ * cgpu_commit builds them, on a host-only context loaded through the map
+ * calls.  Per map entry i, {home slot, the slot stored in} of its frontend
+ * (rows4, rows6: every slave entry reports its frontend), of its endpoint
+ * (rows_e; macs + 16 i: the fwd_macs bytes at that slot) or of its tunnel key
+ * (rows_t); both ~0 for a key the tables do not hold (a key no program
+ * builds).  An endpoint or tunnel key is looked for in its family's table.
+ * stats, three words {mask, relocations, doublings} per table in the order
+ * lb4, lb6, e4, e6, t4, t6 (relocations: lb4 only, else 0). */
+CGPU_EXPORT int cgpu_diag_hop_tables(const cgpu_lb4_key *k4, const cgpu_lb4_service *v4, size_t n4,
+				     const cgpu_lb6_key *k6, const cgpu_lb6_service *v6, size_t n6,
+				     const cgpu_endpoint_key *ek, const cgpu_endpoint_info *ei, size_t ne,
+				     const cgpu_endpoint_key *tk, const cgpu_endpoint_key *tv, size_t nt,
+				     uint32_t *rows4, uint32_t *rows6, uint32_t *rows_e, uint8_t *macs,
+				     uint32_t *rows_t, uint64_t *stats)
+{
+	if ((n4 && (!k4 || !v4 || !rows4)) || (n6 && (!k6 || !v6 || !rows6)) ||
+	    (ne && (!ek || !ei || !rows_e || !macs)) || (nt && (!tk || !tv || !rows_t)) || !stats)
+		return fail(-EINVAL, "null argument");
+	cgpu_config cfg;
+	cgpu_config_default(&cfg);
+	cgpu_ctx *c = nullptr;
+	if (int r = cgpu_ctx_create(&cfg, -1, &c))
+		return r;
+	int rc = 0;
+	for (size_t i = 0; i < n4 && !rc; i++)
+		rc = cgpu_lb4_update(c, &k4[i], &v4[i], CGPU_ANY);
+	for (size_t i = 0; i < n6 && !rc; i++)
+		rc = cgpu_lb6_update(c, &k6[i], &v6[i], CGPU_ANY);
+	for (size_t i = 0; i < ne && !rc; i++)
+		rc = cgpu_endpoint_update_info(c, &ek[i], &ei[i], CGPU_ANY);
+	for (size_t i = 0; i < nt && !rc; i++)
+		rc = cgpu_tunnel_update(c, &tk[i], &tv[i], CGPU_ANY);
+	CommitIn in;
+	if (!rc) {
+		std::lock_guard<std::mutex> g(c->mu);
+		capture(c, in, c->b);
+	}
+	LbBuild lb;
+	Lb6Build lb6;
+	FwdBuild f;
+	if (!rc)
+		rc = build_lb(in.lb, in.cfg.lb_max_entries, lb);
+	if (!rc)
+		rc = build_lb6(in.lb6, in.cfg.lb_max_entries, lb6);
+	if (!rc)
+		build_fwd(in, f);
+	cgpu_ctx_destroy(c);
+	if (rc)
+		return rc;
+	/* the slot of a key among the hop bits of its home; ~0: not stored */
+	auto walk = [](uint32_t home, uint32_t mask, auto hop_of, auto same) {
+		const uint32_t hop = hop_of(home) >> POL_HOP_SHIFT;
+		uint32_t at = ~0u;
+		for (uint32_t d = 0; d < POL_HOP; d++)
+			if (((hop >> d) & 1u) && same((home + d) & mask))
+				at = (home + d) & mask;
+		return at;
+	};
+	for (size_t i = 0; i < n4; i++) {
+		const uint32_t home = lb_hash(k4[i].address, k4[i].dport) & lb.mask;
+		rows4[2 * i] = home;
+		rows4[2 * i + 1] = walk(home, lb.mask, [&](uint32_t s) { return lb.fe[s][3]; }, [&](uint32_t s) {
+			return (lb.fe[s][3] & LB_FE_USED) && lb.fe[s][0] == k4[i].address &&
+			       (lb.fe[s][1] & 0xFFFFu) == k4[i].dport;
+		});
+	}
+	for (size_t i = 0; i < n6; i++) {
+		uint32_t a[4];
+		memcpy(a, k6[i].address, 16);
+		const uint32_t home = lb6_hash(fold6(a[0], a[1], a[2], a[3]), k6[i].dport) & lb6.mask;
+		rows6[2 * i] = home;
+		rows6[2 * i + 1] = walk(home, lb6.mask, [&](uint32_t s) { return lb6.fe[s][6]; }, [&](uint32_t s) {
+			return (lb6.fe[s][6] & LB_FE_USED) && !memcmp(lb6.fe[s].data(), a, 16) &&
+			       (lb6.fe[s][4] & 0xFFFFu) == k6[i].dport;
+		});
+	}
+	auto fwd_rows = [&](const cgpu_endpoint_key &k, bool tunnel, uint32_t *row) {
+		uint32_t a[4];
+		memcpy(a, k.ip, 16);
+		row[0] = row[1] = ~0u;
+		if (k.pad4 || k.pad5)
+			return;
+		if (k.family == 1 && !a[1] && !a[2] && !a[3]) {
+			auto &tab = tunnel ? f.t4 : f.e4;
+			const uint32_t mask = tunnel ? f.t4_mask : f.e4_mask;
+			row[0] = fwd_hash4(a[0]) & mask;
+			row[1] = walk(row[0], mask, [&](uint32_t s) { return tab[s][3]; },
+				      [&](uint32_t s) { return (tab[s][3] & FWD_USED) && tab[s][0] == a[0]; });
+		} else if (k.family == 2 && !(tunnel && a[3])) {
+			auto &tab = tunnel ? f.t6 : f.e6;
+			const uint32_t mask = tunnel ? f.t6_mask : f.e6_mask;
+			row[0] = fold6(a[0], a[1], a[2], tunnel ? 0u : a[3]) & mask;
+			row[1] = walk(row[0], mask, [&](uint32_t s) { return tab[s][6]; }, [&](uint32_t s) {
+				return (tab[s][6] & FWD_USED) && !memcmp(tab[s].data(), a, tunnel ? 12 : 16);
+			});
+		}
+	};
+	for (size_t i = 0; i < ne; i++) {
+		fwd_rows(ek[i], false, rows_e + 2 * i);
+		memset(macs + 16 * i, 0, 16);
+		if (rows_e[2 * i + 1] != ~0u)
+			memcpy(macs + 16 * i, (ek[i].family == 1 ? f.m4 : f.m6)[rows_e[2 * i + 1]].data(), 16);
+	}
+	for (size_t i = 0; i < nt; i++)
+		fwd_rows(tk[i], true, rows_t + 2 * i);
+	const uint64_t st[18] = {lb.mask,   lb.relocations, lb.doublings,
+				 lb6.mask,  0,              lb6.doublings,
+				 f.e4_mask, 0,              f.e4_doublings,
+				 f.e6_mask, 0,              f.e6_doublings,
+				 f.t4_mask, 0,              f.t4_doublings,
+				 f.t6_mask, 0,              f.t6_doublings};
+	memcpy(stats, st, sizeof(st));
+	return 0;
 }
 
 CGPU_EXPORT int cgpu_counter_layout_checksum(cgpu_ctx *c, uint64_t *sum)
