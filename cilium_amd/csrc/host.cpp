@@ -572,9 +572,16 @@ struct PolBuild {
 	}
 	/* CGPU_POL_SLOTS_PER_KEY slots per key: at 8 (<= 12.5 % load) nearly
 	 * every key sits in its home slot, one gather per probe.  Denser tables
-	 * measured slower although smaller (config 2, one session, no rebalance:
-	 * 2 MiB 1.80 ms, 4 MiB 1.75, 8 MiB 1.72; profiles/r6_d/ab.log): a key
-	 * displaced from its home slot costs a dependent second gather */
+	 * cost every path that resolves per tuple (pol_resolve1) a dependent
+	 * second gather for each displaced key: at 2 slots per key (config 2:
+	 * 2 MiB instead of 8) cascade measured 2.94 -> 3.11 ms, frames 2.49 ->
+	 * 2.63, v6 2.68 -> 2.75, ct 10.36 -> 10.72 (bench.py pairs,
+	 * profiles/pol_density/bench_ab_dense2.json).  The plain x4 kernel, whose
+	 * hop rounds cost one gather per lane, gained 0.005-0.017 ms of 1.43
+	 * from the smaller table although its L2 misses fell by 11M per launch
+	 * (2 MiB 1.412-1.425 ms, 4 MiB 1.421-1.426, 8 MiB 1.429-1.431;
+	 * ab_density_rounds.log there): not enough to build it its own table.
+	 * (profiles/r6_d/ab.log, before the quad-wide stages: 1.80 / 1.75 / 1.72) */
 	void build(const std::vector<PolKey> &keys)
 	{
 		uint32_t nb = next_pow2(std::max<uint64_t>(64, (uint64_t)CGPU_POL_SLOTS_PER_KEY * keys.size() + 2));

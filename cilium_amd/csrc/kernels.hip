@@ -224,34 +224,17 @@ template <int Q> __device__ __forceinline__ void whole_q(uint4 (&v)[Q])
 	}
 }
 
-/* One 16-byte gather per tuple of a quad, the Q loads back to back: every
- * address is in registers before the first load (address arithmetic between
- * the loads reuses registers that an earlier load still owes, which the
- * compiler then waits for), and all the loaded words are wanted at once */
-template <int Q> __device__ __forceinline__ void gather_q(const uint4 *(&p)[Q], uint4 (&x)[Q])
-{
-	if constexpr (Q == 4)
-		asm volatile("" : "+v"(p[0]), "+v"(p[1]), "+v"(p[2]), "+v"(p[3]));
-	/* (device memory: the statement above hides where p points) */
-	typedef const __attribute__((address_space(1))) v4u_t *gx4;
-#pragma unroll
-	for (int u = 0; u < Q; u++) {
-		const v4u_t v = *(gx4)p[u];
-		x[u] = make_uint4(v.x, v.y, v.z, v.w);
-	}
-	whole_q<Q>(x);
-}
-
 /* pol_resolve1 over the Q tuples of a lane (k_classify_x4): want[u] tuples
  * resolve {lo[u], hi[u], ep[u]} from their home slot sl[u] (index b[u]) into
- * ctr[u] / z[u]; the others keep theirs.  The hop slots are read in rounds:
- * every tuple that still has hop bits loads ONE candidate slot, all Q loads
- * issued together and then compared, so a round is one round trip for the
- * quad and not one per tuple and hop.  A tuple with no bits left loads slot 0
- * (branch-free: a branch around a tuple's load makes the compiler wait for
- * it before the next tuple's is issued).  A tuple's candidates come in the
- * order of pol_resolve1 and its first match ends them.  The loop's condition
- * is wave-uniform. */
+ * ctr[u] / z[u]; the others keep theirs.  The hop slots are read in rounds
+ * of ONE gather per lane: almost always at most one of a lane's Q tuples
+ * still has hop bits, so a round takes the lane's first such tuple, loads
+ * one candidate slot of it and compares; a lane with two pending tuples
+ * takes them in successive rounds.  A tuple's candidates come in the order
+ * of pol_resolve1 and its first match ends them.  The loop's condition is
+ * wave-uniform.  (Rounds that load one candidate of every pending tuple, Q
+ * gathers per lane and three of them for nothing, measured 0.015 ms slower
+ * at config 2: profiles/pol_density/ab_density_rounds.log.) */
 template <int Q>
 __device__ __forceinline__ void pol_resolve_q(const pol_table &t, const uint4 (&sl)[Q], const uint32_t (&b)[Q],
 					      const uint32_t (&lo)[Q], const uint32_t (&hi)[Q],
@@ -272,21 +255,30 @@ __device__ __forceinline__ void pol_resolve_q(const pol_table &t, const uint4 (&
 		any |= hop[u];
 	}
 	while (__ballot(any != 0u)) {
-		uint4 x[Q];
-		const uint4 *p[Q];
+		/* the lane's first tuple with bits left, its words in scalars of the lane */
+		uint32_t sb = b[Q - 1], slo = lo[Q - 1], shi = hi[Q - 1], sep = ep[Q - 1], shop = hop[Q - 1];
+		int su = Q - 1;
 #pragma unroll
-		for (int u = 0; u < Q; u++) {
-			const uint32_t j = hop[u] ? (uint32_t)__builtin_ctz(hop[u]) : 0u;
-			p[u] = tab + (hop[u] ? (b[u] + j) & t.bucket_mask : 0u);
+		for (int u = Q - 2; u >= 0; u--) {
+			const bool p = hop[u] != 0u;
+			sb = p ? b[u] : sb;
+			slo = p ? lo[u] : slo;
+			shi = p ? hi[u] : shi;
+			sep = p ? ep[u] : sep;
+			shop = p ? hop[u] : shop;
+			su = p ? u : su;
 		}
-		gather_q<Q>(p, x);
+		uint4 x = make_uint4(0, 0, 0, 0);
+		if (shop) /* (a lane with nothing pending issues no load) */
+			x = tab[(sb + (uint32_t)__builtin_ctz(shop)) & t.bucket_mask];
+		const bool hit = shop && x.x == slo && x.y == shi && (x.z & 0xFFFFu) == sep;
 		any = 0u;
 #pragma unroll
 		for (int u = 0; u < Q; u++) {
-			const bool hit = hop[u] && x[u].x == lo[u] && x[u].y == hi[u] && (x[u].z & 0xFFFFu) == ep[u];
-			z[u] = hit ? x[u].z : z[u];
-			ctr[u] = hit ? (int)(x[u].w & POL_CTR_MASK) : ctr[u];
-			hop[u] = hit ? 0u : hop[u] & (hop[u] - 1u);
+			const bool mine = su == u && shop;
+			z[u] = mine && hit ? x.z : z[u];
+			ctr[u] = mine && hit ? (int)(x.w & POL_CTR_MASK) : ctr[u];
+			hop[u] = mine ? (hit ? 0u : hop[u] & (hop[u] - 1u)) : hop[u];
 			any |= hop[u];
 		}
 	}
@@ -294,7 +286,8 @@ __device__ __forceinline__ void pol_resolve_q(const pol_table &t, const uint4 (&
 
 /* pg_resolve over the Q tuples of a lane, in the rounds of pol_resolve_q:
  * g[u] (home slot, index b[u]) becomes the group slot of {id[u], ed[u]} or
- * {0, 0, EMPTY, 0}; tuples with want[u] clear keep theirs. */
+ * {0, 0, EMPTY, 0}; tuples with want[u] clear keep theirs.  (Q gathers per
+ * lane and round: 0.010-0.016 ms slower, ab_pg_rounds.log there.) */
 template <int Q>
 __device__ __forceinline__ void pg_resolve_q(const pol_groups &t, uint4 (&g)[Q], const uint32_t (&b)[Q],
 					     const uint32_t (&id)[Q], const uint32_t (&ed)[Q],
@@ -312,23 +305,30 @@ __device__ __forceinline__ void pg_resolve_q(const pol_groups &t, uint4 (&g)[Q],
 		any |= hop[u];
 	}
 	while (__ballot(any != 0u)) {
-		uint4 x[Q];
-		const uint4 *p[Q];
+		uint32_t sb = b[Q - 1], sid = id[Q - 1], sed = ed[Q - 1], shop = hop[Q - 1];
+		int su = Q - 1;
 #pragma unroll
-		for (int u = 0; u < Q; u++) {
-			const uint32_t j = hop[u] ? (uint32_t)__builtin_ctz(hop[u]) : 0u;
-			p[u] = t.slots + (hop[u] ? (b[u] + j) & t.mask : 0u);
+		for (int u = Q - 2; u >= 0; u--) {
+			const bool p = hop[u] != 0u;
+			sb = p ? b[u] : sb;
+			sid = p ? id[u] : sid;
+			sed = p ? ed[u] : sed;
+			shop = p ? hop[u] : shop;
+			su = p ? u : su;
 		}
-		gather_q<Q>(p, x);
+		uint4 x = make_uint4(0, 0, 0, 0);
+		if (shop)
+			x = t.slots[(sb + (uint32_t)__builtin_ctz(shop)) & t.mask];
+		const bool hit = shop && x.x == sid && (x.y & 0x1FFFFu) == sed;
 		any = 0u;
 #pragma unroll
 		for (int u = 0; u < Q; u++) {
-			const bool hit = hop[u] && x[u].x == id[u] && (x[u].y & 0x1FFFFu) == ed[u];
-			g[u].x = hit ? x[u].x : g[u].x;
-			g[u].y = hit ? x[u].y : g[u].y;
-			g[u].z = hit ? x[u].z : g[u].z;
-			g[u].w = hit ? x[u].w : g[u].w;
-			hop[u] = hit ? 0u : hop[u] & (hop[u] - 1u);
+			const bool mine = su == u && shop;
+			g[u].x = mine && hit ? x.x : g[u].x;
+			g[u].y = mine && hit ? x.y : g[u].y;
+			g[u].z = mine && hit ? x.z : g[u].z;
+			g[u].w = mine && hit ? x.w : g[u].w;
+			hop[u] = mine ? (hit ? 0u : hop[u] & (hop[u] - 1u)) : hop[u];
 			any |= hop[u];
 		}
 	}

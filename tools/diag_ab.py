@@ -74,10 +74,18 @@ VARIANTS = {"product": (), "no_cold_atomics": ("CGPU_DIAG_NO_COLD",),
             # (svc_q1, the per-lane service prep: ctlb 20.61 against 20.40 ms: r5_k/ab_ctlb_svc_q.log)
             # (svc_pre6_off, the IPv6 service prep without the trie pre-pass: ctlb6 22.46 against 22.16 ms: r5_k/ab_ctlb6_pre6.log)
             "ff_h1": ("CGPU_FF_H=1",), "ff_h4": ("CGPU_FF_H=4",),
-            # policy table slots per key (hopscotch, round 6): 2 = 2 MiB at config 2
-            # (the product), 4 = 4 MiB, 8 = 8 MiB (round 5's footprint)
+            # policy table slots per key (hopscotch, round 6): 8 = 8 MiB at config 2
+            # (the product), 4 = 4 MiB, 2 = 2 MiB
             "pol_spk4": ("CGPU_POL_SLOTS_PER_KEY=4",), "pol_spk8": ("CGPU_POL_SLOTS_PER_KEY=8",),
             "pol_spk2": ("CGPU_POL_SLOTS_PER_KEY=2",),
+            # (pol_quad_rounds / pg_quad_rounds, the plain kernel's hop rounds of the key
+            # table / the group table with one gather per tuple instead of one per lane:
+            # 1.428-1.434 against 1.412-1.425 ms, 1.399-1.406 against 1.389-1.390, at every
+            # table size: profiles/pol_density/ab_density_rounds.log, ab_pg_rounds.log; the
+            # macros left the tree with the result)
+            # (pol_dense2 / pol_dense4, 2 / 4 slots per key for key sets past 65,536 slots
+            # only: the plain kernel 0.005-0.017 ms faster, every per-tuple path 1.5-5.6 %
+            # slower: profiles/pol_density/bench_ab_dense2.json; not kept)
             # (v6_pre_nospec, the v6 pre-pass's addresses loaded behind the direction flag, round 5's form: 2.837 against 2.809 ms: r6_h/ab_v6_pre.log)
             "v6_pre_q3": ("CGPU_DIAG_IPC6_PRE_Q=3",), "v6_pre_q4b": ("CGPU_DIAG_IPC6_PRE_Q=4",),
             # LB frontend slots per frontend (hopscotch, round 6): 2 = 32 MiB at config 5
@@ -312,7 +320,8 @@ def run(names):
         ms = sorted(a.elapsed_time(b) for a, b in ev)
         med = ms[reps // 2]
         print(json.dumps({"variant": name, "median_ms": round(med, 4), "min_ms": round(ms[0], 4),
-                          "gpps": round(n / med / 1e6, 2), "launches": reps}), flush=True)
+                          "gpps": round(n / med / 1e6, 2), "launches": reps,
+                          "policy_bytes": int(e.table_bytes()["policy"])}), flush=True)
         e.close()
 
 
