@@ -116,6 +116,15 @@ class Frames(C.Structure):
                 ("ep", C.c_void_p), ("stride", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class FlbIn(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("len", C.c_void_p), ("flags", C.c_void_p), ("ep", C.c_void_p),
+                ("stride", C.c_uint32), ("reserved", C.c_uint32), ("hash", C.c_void_p)]
+
+
+class FlbOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("lb_ret", "rev_nat", "slave")]
+
+
 class FrameTuples(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in
                 ("status", "family", "saddr", "daddr", "dport", "proto", "flags")]
@@ -226,6 +235,7 @@ PROTOS = {
     "cgpu_frames_parse": (i32, [vp, C.POINTER(Frames), sz, C.POINTER(FrameTuples), vp]),
     "cgpu_classify_frames": (i32, [vp, C.POINTER(Frames), sz, vp, vp, vp, vp]),
     "cgpu_classify_frames_host": (i32, [vp, C.POINTER(Frames), sz, vp, vp, vp, vp]),
+    "cgpu_classify_frames_lb": (i32, [vp, C.POINTER(FlbIn), u32, sz, vp, vp, vp, C.POINTER(FlbOut), vp]),
     "cgpu_ct4_update": (i32, [vp, vp, vp, u64]),
     "cgpu_ct4_delete": (i32, [vp, vp]),
     "cgpu_ct4_lookup": (i32, [vp, vp, vp]),

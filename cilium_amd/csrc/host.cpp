@@ -6216,6 +6216,55 @@ CGPU_EXPORT int cgpu_classify_frames(cgpu_ctx *c, const cgpu_frames *f, size_t n
 	return frames_enqueue(c, P.snap(), P.delta, P.pk, f, n, verdict, identity, stage, (hipStream_t)stream);
 }
 
+/* the service step on raw frames (cgpu.h cgpu_classify_frames_lb): the whole
+ * call is judged before the context, as cgpu_forward_frames is */
+CGPU_EXPORT int cgpu_classify_frames_lb(cgpu_ctx *c, const cgpu_flb_in *in, uint32_t flags, size_t n,
+					int32_t *verdict, uint32_t *identity, uint8_t *stage,
+					const cgpu_flb_out *lb, void *stream)
+{
+	if (!c || !in)
+		return fail(-EINVAL, "null argument");
+	if ((flags & ~CGPU_FLB_REWRITE) || in->reserved)
+		return fail(-EINVAL, "unknown flags 0x%x or nonzero reserved", flags);
+	if (in->stride < 64 || (in->stride & 15))
+		return fail(-EINVAL, "frame stride must be a multiple of 16 and >= 64");
+	if ((uintptr_t)in->data & 15)
+		return fail(-EINVAL, "frame buffer must be 16-byte aligned");
+	if (n && (!in->data || !in->len || !in->flags || !in->ep || !verdict || !identity))
+		return fail(-EINVAL, "null data, len, flags, ep, verdict or identity column");
+	if (((uintptr_t)in->len | (uintptr_t)in->hash | (uintptr_t)verdict | (uintptr_t)identity |
+	     (uintptr_t)(lb ? lb->lb_ret : nullptr)) & 3u)
+		return fail(-EINVAL, "4-byte column not 4-byte aligned");
+	if (((uintptr_t)in->ep | (uintptr_t)(lb ? lb->rev_nat : nullptr) | (uintptr_t)(lb ? lb->slave : nullptr)) & 1u)
+		return fail(-EINVAL, "2-byte column not 2-byte aligned");
+	Pinned P;
+	if (int r = pin(c, stream, P, true))
+		return r;
+	if (!n)
+		return 0;
+	frames_lb_args a{};
+	a.data = in->data;
+	a.len = in->len;
+	a.flags = in->flags;
+	a.ep = in->ep;
+	a.hash = in->hash;
+	a.stride = in->stride;
+	a.rewrite = flags & CGPU_FLB_REWRITE;
+	a.n = n;
+	a.verdict = verdict;
+	a.identity = identity;
+	a.stage = stage;
+	if (lb) {
+		a.lb_ret = lb->lb_ret;
+		a.rev_nat = lb->rev_nat;
+		a.slave = lb->slave;
+	}
+	a.delta = P.delta;
+	a.pk = P.pk;
+	HIP_OR_EIO(launch_classify_frames_lb(P.snap(), a, (hipStream_t)stream));
+	return 0;
+}
+
 CGPU_EXPORT int cgpu_classify_frames_host(cgpu_ctx *c, const cgpu_frames *f, size_t n, int32_t *verdict,
 					  uint32_t *identity, uint8_t *stage, void *stream)
 {

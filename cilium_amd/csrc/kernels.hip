@@ -4269,6 +4269,599 @@ __global__ __launch_bounds__(BLOCK) void k_forward_frames(fwd_tables F, fwd_macs
 	}
 }
 
+/* ------------------------------------------------------------------ */
+/* the service step on raw frames (cgpu_classify_frames_lb)            */
+/* ------------------------------------------------------------------ */
+#define DROP_CSUM_L4 (-154)
+
+/* parse_frame_w cut in two around the service step: parse_frame_pre is its
+ * steps up to and including extract_l4_port (and hands out the L4 offset and
+ * the key dport it loaded), parse_frame_post the ct_lookup port extraction
+ * and protocol gate.  A copy beside parse_frame_w and not a split of it: the
+ * fused frames kernel sits at its register budget and stays as
+ * it compiles today.  A change of the parse goes into both. */
+__device__ __forceinline__ ftuple parse_frame_pre(const cgpu_snapshot &s, const fwin &W, const uint8_t *f,
+						  uint32_t len, uint32_t cap, bool egress, uint32_t ep,
+						  const uint4 *lxc, uint32_t &l4, bool &inwin, uint32_t &kd)
+{
+	ftuple t;
+	t.status = 0;
+	t.fam = 0;
+	t.sa = uint4{0, 0, 0, 0};
+	t.da = uint4{0, 0, 0, 0};
+	t.dport = 0;
+	t.proto = 0;
+	t.frag = false;
+	l4 = 0;
+	inwin = false;
+	kd = 0;
+	if (len < 14u) {
+		t.status = DROP_INVALID;
+		return t;
+	}
+	const uint32_t et = W.h(12);
+	const bool v4 = et == 0x0008u;
+	if (!v4 && et != 0xDD86u) {
+		t.status = (egress && et != 0x0608u) ? DROP_UNKNOWN_L3 : FRAME_NOT_CLASSIFIED;
+		return t;
+	}
+	t.fam = v4 ? 4u : 6u;
+	if (len < (v4 ? 34u : 54u)) {
+		t.status = DROP_INVALID;
+		return t;
+	}
+	if (v4) {
+		t.sa.x = W.d(26);
+		t.da.x = W.d(30);
+		t.proto = W.b(23);
+	} else {
+		t.sa = uint4{W.d(22), W.d(26), W.d(30), W.d(34)};
+		t.da = uint4{W.d(38), W.d(42), W.d(46), W.d(50)};
+		t.proto = W.b(20);
+	}
+	if (egress && !v4 && t.proto == 58u) { /* handle_ipv6's ICMPv6 responders */
+		int32_t r = len < 62u ? DROP_INVALID : 0;
+		if (!r) {
+			const uint32_t type = W.b(54);
+			if (type == 135u) {
+				r = fchk(62u, 16u, len, cap, DROP_INVALID);
+				if (!r) {
+					uint32_t diff = 0;
+#pragma unroll
+					for (int k = 0; k < 4; k++) {
+						const uint32_t w = (uint32_t)f[62 + 4 * k] | (uint32_t)f[63 + 4 * k] << 8 |
+								   (uint32_t)f[64 + 4 * k] << 16 |
+								   (uint32_t)f[65 + 4 * k] << 24;
+						diff |= w ^ s.router_ip[k];
+					}
+					r = diff ? DROP_UNKNOWN_TARGET : fchk(78u, 8u, len, cap, DROP_INVALID);
+					if (!r)
+						r = FRAME_NOT_CLASSIFIED;
+				}
+			} else if (type == 128u && t.da.x == s.router_ip[0] && t.da.y == s.router_ip[1] &&
+				   t.da.z == s.router_ip[2] && t.da.w == s.router_ip[3]) {
+				r = FRAME_NOT_CLASSIFIED;
+			}
+		}
+		if (r) {
+			t.status = r;
+			return t;
+		}
+	}
+	if (egress && ep < s.n_lxc) { /* SMAC / DMAC / SIP checks of the endpoint */
+		const uint4 i0 = lxc[2u * ep];
+		const uint32_t verify = (i0.y >> 16) & 0xffu;
+		if ((verify & CGPU_VERIFY_SMAC) && (W.d(6) != i0.x || W.h(10) != (i0.y & 0xffffu))) {
+			t.status = DROP_INVALID_SMAC;
+			return t;
+		}
+		if ((verify & CGPU_VERIFY_DMAC) && (W.d(0) != s.node_mac_lo || W.h(4) != s.node_mac_hi)) {
+			t.status = DROP_INVALID_DMAC;
+			return t;
+		}
+		if (verify & CGPU_VERIFY_SIP) {
+			bool ok;
+			if (v4) {
+				ok = t.sa.x == i0.z;
+			} else {
+				const uint4 i1 = lxc[2u * ep + 1u];
+				ok = t.sa.x == i0.w && t.sa.y == i1.x && t.sa.z == i1.y && t.sa.w == i1.z;
+			}
+			if (!ok) {
+				t.status = DROP_INVALID_SIP;
+				return t;
+			}
+		}
+	}
+	if (v4) {
+		l4 = 14u + 4u * (W.b(14) & 15u);
+		inwin = l4 == 34u;
+		t.frag = !egress && (W.h(20) & 0xFFBFu) != 0u;
+	} else { /* ipv6_hdrlen */
+		uint32_t nh = t.proto, off = 40u;
+		int32_t r = 1;
+		for (int k = 0; k < 4 && r == 1; k++) {
+			if (nh == 59u) {
+				r = DROP_INVALID_EXTHDR;
+			} else if (nh == 44u) {
+				r = DROP_FRAG_NOSUPPORT;
+			} else if (nh == 0u || nh == 43u || nh == 51u || nh == 60u) {
+				const uint32_t o = 14u + off;
+				r = fchk(o, 2, len, cap, DROP_INVALID);
+				if (!r) {
+					const uint32_t hl = f[o + 1];
+					nh = f[o];
+					off += nh == 51u ? (hl + 2u) << 2 : (hl + 1u) << 3;
+					r = 1;
+				}
+			} else {
+				r = 0;
+			}
+		}
+		if (r == 1)
+			r = DROP_INVALID_EXTHDR;
+		if (r) {
+			t.status = r;
+			return t;
+		}
+		t.proto = nh;
+		l4 = 14u + off;
+		inwin = l4 == 54u;
+	}
+	/* extract_l4_port of lb{4,6}_extract_key under LB_L4 */
+	if (egress && (s.lb_flags & CGPU_LB_L4) && (t.proto == 6u || t.proto == 17u)) {
+		const int32_t r = fchk(l4 + 2u, 2, len, cap, EFAULT_LOAD);
+		if (r) {
+			t.status = r;
+			return t;
+		}
+		kd = inwin ? (v4 ? W.h(36) : W.h(56)) : (uint32_t) * reinterpret_cast<const uint16_t *>(f + l4 + 2u);
+	}
+	return t;
+}
+
+/* ct_lookup{4,6}'s port extraction and protocol gate on a frame that
+ * parse_frame_pre passed (parse_frame_w's last step).  It reads the frame as
+ * it was loaded; the caller puts a translated dport in afterwards. */
+__device__ __forceinline__ void parse_frame_post(const cgpu_snapshot &s, const fwin &W, const uint8_t *f, ftuple &t,
+						 uint32_t l4, bool inwin, uint32_t len, uint32_t cap)
+{
+	if (!s.ct_proto_gate)
+		return;
+	const bool v4 = t.fam == 4u;
+	int32_t r;
+	if (t.proto == (v4 ? 1u : 58u)) {
+		if ((r = fchk(l4, 1, len, cap, DROP_CT_INVALID_HDR))) {
+			t.status = r;
+			return;
+		}
+		const uint32_t type = inwin ? (v4 ? W.b(34) : W.b(54)) : (uint32_t)f[l4];
+		t.dport = type == (v4 ? 8u : 128u) ? type : 0u;
+	} else if (t.proto == 6u || t.proto == 17u) {
+		if ((r = fchk(l4, t.proto == 6u ? 14u : 4u, len, cap, DROP_CT_INVALID_HDR))) {
+			t.status = r;
+			return;
+		}
+		t.dport = inwin ? (v4 ? W.h(36) : W.h(56)) : (uint32_t) * reinterpret_cast<const uint16_t *>(f + l4 + 2u);
+	} else {
+		t.status = DROP_CT_UNKNOWN_PROTO;
+	}
+}
+
+/* The service step's result for the rewrite: lb4_one<CGPU_LB_LXC> / lb6_one
+ * handing out what lb{4,6}_xlate read beyond their results -- the chosen
+ * entry's port and, in kd, key.dport as lb{4,6}_lookup_service left it (0
+ * once the L3 key answered: l4_modify_port patches the checksum from that
+ * value, not from the packet's port) -- and for IPv6 the entry's
+ * rev_nat_index and slave.  The caller has tested the vip bitmap.  Copies and
+ * not wrappers under lb4_one / lb6_one, as fwd_slot4 is of fwd_find4: the
+ * classify kernels that call those stay as they compile today.  A change of
+ * the service step goes into both. */
+struct lbf_res {
+	int32_t ret;             /* 0, CGPU_LB_XLATED, CGPU_LB_XLATED_LOOPBACK, DROP_NO_SERVICE */
+	uint4 daddr;             /* the chosen entry's target (IPv4 in .x) */
+	uint32_t port, kd;       /* svc->port, key.dport after the lookups */
+	uint32_t rev_nat, slave;
+};
+
+__device__ __forceinline__ lbf_res lb4_one_sel(const cgpu_snapshot &s, uint32_t sa, uint32_t da, uint32_t dp,
+					       uint32_t proto, uint32_t hash)
+{
+	lbf_res r{0, uint4{da, 0, 0, 0}, 0, 0, 0, 0};
+	uint32_t kd = 0, probes = 0;
+	if (s.lb_flags & CGPU_LB_L4) {
+		if (proto == 6u || proto == 17u)
+			kd = dp;
+		else if (proto != 1u && proto != 58u)
+			return r;
+	}
+	uint4 f, v;
+	if (!lb_service(s, da, &kd, 0, &v, &f, &probes))
+		return r;
+	if (s.ct_proto_gate && proto != 1u && proto != 6u && proto != 17u) {
+		r.ret = DROP_NO_SERVICE;
+		return r;
+	}
+	uint32_t slave = hash % (v.y >> 16) + 1u;
+	uint4 b;
+	if (!lb_entry(s.lb, f, slave, &b)) {
+		if (!lb_service(s, da, &kd, slave, &b, &f, &probes)) {
+			r.ret = DROP_NO_SERVICE;
+			return r;
+		}
+		slave = hash % (b.y >> 16) + 1u;
+	}
+	r.ret = sa == b.x ? CGPU_LB_XLATED_LOOPBACK : CGPU_LB_XLATED;
+	r.daddr.x = b.x;
+	r.port = b.y & 0xFFFFu;
+	r.kd = kd;
+	r.rev_nat = b.z & 0xFFFFu;
+	r.slave = slave;
+	return r;
+}
+
+__device__ __forceinline__ lbf_res lb6_one_sel(const cgpu_snapshot &s, uint4 da, uint32_t dp, uint32_t proto,
+					       uint32_t hash)
+{
+	lbf_res r{0, da, 0, 0, 0, 0};
+	uint32_t kd = 0;
+	if (s.lb_flags & CGPU_LB_L4) {
+		if (proto == 6u || proto == 17u)
+			kd = dp;
+		else if (proto != 1u && proto != 58u)
+			return r;
+	}
+	const uint32_t f = fold6(da.x, da.y, da.z, da.w);
+	uint4 tg, val;
+	if (!lb6_service(s, da, f, &kd, 0, tg, val))
+		return r;
+	if (s.ct_proto_gate && proto != 58u && proto != 6u && proto != 17u) {
+		r.ret = DROP_NO_SERVICE;
+		return r;
+	}
+	uint32_t slave = hash % (val.x >> 16) + 1u;
+	if (!lb6_get(s.lb6, da, f, kd, slave, tg, val)) {
+		if (!lb6_service(s, da, f, &kd, slave, tg, val)) {
+			r.ret = DROP_NO_SERVICE;
+			return r;
+		}
+		slave = hash % (val.x >> 16) + 1u; /* lb.h:467 */
+	}
+	r.ret = CGPU_LB_XLATED;
+	r.daddr = tg;
+	r.port = val.x & 0xFFFFu;
+	r.kd = kd;
+	r.rev_nat = val.y & 0xFFFFu;
+	r.slave = slave;
+	return r;
+}
+
+__device__ __forceinline__ uint32_t csum_fold_not(uint32_t t)
+{
+	t = (t & 0xFFFFu) + (t >> 16);
+	t = (t & 0xFFFFu) + (t >> 16);
+	return ~t & 0xFFFFu;
+}
+
+/* The L4 checksum field c (as loaded) through lb{4,6}_xlate's patches: the
+ * address diff D (l4_csum_replace(off, 0, D, BPF_F_PSEUDO_HDR)) when `addr`,
+ * then the port (l4_csum_replace(off, from, to, 2)) when `port`.  UDP carries
+ * BPF_F_MARK_MANGLED_0: a field of 0 stays 0, a patch that yields 0 stores
+ * 0xFFFF (cgpu.h cgpu_classify_frames_lb has the arithmetic). */
+__device__ __forceinline__ uint32_t csum_l4_xlate(uint32_t c, uint32_t D, bool addr, bool port, uint32_t from,
+						  uint32_t to, bool udp)
+{
+	if (udp && !c)
+		return 0u;
+	if (addr) {
+		c = csum_fold_not(csum_add32(D, ~c));
+		if (udp && !c)
+			c = 0xFFFFu;
+	}
+	if (port) {
+		c = csum_fold_not(csum_add32(csum_add32(~c, ~from), to));
+		if (udp && !c)
+			c = 0xFFFFu;
+	}
+	return c;
+}
+
+/* the u16 at the even offset o of [32, 64) in the window, and its store */
+__device__ __forceinline__ uint32_t fwin_get16(const fwin &W, uint32_t o)
+{
+	uint32_t w = 0;
+#pragma unroll
+	for (int k = 8; k < 16; k++)
+		w = (o >> 2) == (uint32_t)k ? W.w[k] : w;
+	return (w >> ((o & 2u) * 8u)) & 0xFFFFu;
+}
+
+__device__ __forceinline__ void fwin_put16(fwin &W, uint32_t o, uint32_t v)
+{
+	const uint32_t sh = (o & 2u) * 8u;
+#pragma unroll
+	for (int k = 8; k < 16; k++)
+		W.w[k] = (o >> 2) == (uint32_t)k ? (W.w[k] & ~(0xFFFFu << sh)) | (v << sh) : W.w[k];
+}
+
+__device__ __forceinline__ void st_h(uint8_t *p, uint32_t v) { *reinterpret_cast<uint16_t *>(p) = (uint16_t)v; }
+
+/* cgpu_classify_frames_lb (cgpu.h has the rules): k_frames<1, NT> with the
+ * egress service step between extract_l4_port and ct_lookup, and with RW the
+ * bytes lb4_xlate / lb6_xlate write.  One frame per lane in batch order,
+ * grid-stride; counters and metrics as k_frames<1, NT>.
+ *
+ * The vip bitmap word of the frame's daddr, the service lookup's first
+ * gather, is loaded by every lane from the window before the parse decides
+ * anything (a frame that is not IP reads the word of whatever lies there and
+ * drops it); lb4_one_sel / lb6_one_sel then run only where its bit is set.
+ *
+ * Every new value is computed from the frame as it was loaded, and the
+ * stores follow in the reference's order.  An option-less IPv4 / extension-
+ * less IPv6 frame is rewritten in the window and stores the 16-byte words it
+ * changed; the one field of such a frame that lies past the first 64 bytes,
+ * the TCP checksum of an IPv6 frame at byte 70, and every field of a frame
+ * with IPv4 options or IPv6 extension headers go by halfword accesses. */
+template <bool RW, int NT>
+__global__ __launch_bounds__(NT) void k_frames_lb(cgpu_snapshot s, frames_lb_args a)
+{
+	extern __shared__ __attribute__((aligned(16))) uint64_t lctr[];
+	uint64_t mcnt[6] = {0, 0, 0, 0, 0, 0}, mbyt[6] = {0, 0, 0, 0, 0, 0};
+	uint64_t *met = a.delta + 2ull * s.n_ctr_slots;
+	for (uint32_t k = threadIdx.x; k < s.hot_slots; k += NT)
+		lctr[k] = 0;
+	__syncthreads();
+	const uint64_t gstride = (uint64_t)gridDim.x * NT;
+	for (uint64_t i = (uint64_t)blockIdx.x * NT + threadIdx.x; i < a.n; i += gstride) {
+		uint8_t *f = a.data + i * (uint64_t)a.stride;
+		fwin W;
+#pragma unroll
+		for (int k = 0; k < 4; k++) {
+			const uint4 v = ld_x4<true>(f + 16 * k);
+			W.w[4 * k] = v.x;
+			W.w[4 * k + 1] = v.y;
+			W.w[4 * k + 2] = v.z;
+			W.w[4 * k + 3] = v.w;
+		}
+		const uint32_t len = a.len[i];
+		const bool egress = a.flags[i] & 1u;
+		const uint32_t ep = a.ep[i];
+		const uint32_t cap = min(len, a.stride);
+		const uint32_t hcol = a.hash ? a.hash[i] : 0u;
+
+		const bool w4 = W.h(12) == 0x0008u;
+		const uint32_t vb = w4 ? lb_vip_bit(W.d(30)) & s.lb.vip_mask
+				       : lb6_vip_bit(fold6(W.d(38), W.d(42), W.d(46), W.d(50))) & s.lb6.vip_mask;
+		const uint32_t vipw = (w4 ? s.lb.vip : s.lb6.vip)[vb >> 5];
+
+		uint32_t l4, kd;
+		bool inwin;
+		ftuple t = parse_frame_pre(s, W, f, len, cap, egress, ep, s.lxc, l4, inwin, kd);
+		const bool v4 = t.fam == 4u;
+		int32_t lbr = 0;
+		uint32_t rnat = 0, slave = 0, st_lb = 0, pnew = 0;
+		bool pdone = false; /* the step stored a new dport */
+		if (t.status == 0 && egress && ((vipw >> (vb & 31u)) & 1u)) {
+			const bool tu = t.proto == 6u || t.proto == 17u;
+			uint32_t h = hcol;
+			if (!a.hash) {
+				/* cgpu_flow_hash / _hash6 over the frame's own fields; the
+				 * sport is read where the wire has it */
+				uint32_t sp = 0;
+				if (tu && l4 + 2u <= cap)
+					sp = inwin ? (v4 ? W.h(34) : W.h(54))
+						   : (uint32_t) * reinterpret_cast<const uint16_t *>(f + l4);
+				h = v4 ? flow_hash(t.sa.x, t.da.x, sp, kd, t.proto)
+				       : flow_hash(fold6(t.sa.x, t.sa.y, t.sa.z, t.sa.w),
+						   fold6(t.da.x, t.da.y, t.da.z, t.da.w), sp, kd, t.proto);
+			}
+			uint32_t nsa = 0, nport = 0, kdf = 0;
+			uint4 nda = t.da;
+			bool loop = false;
+			{
+				const lbf_res r = v4 ? lb4_one_sel(s, t.sa.x, t.da.x, kd, t.proto, h)
+						     : lb6_one_sel(s, t.da, kd, t.proto, h);
+				lbr = r.ret;
+				if (lbr > 0) {
+					nda = r.daddr;
+					loop = lbr == CGPU_LB_XLATED_LOOPBACK;
+					nsa = s.ipv4_loopback;
+					nport = r.port;
+					kdf = r.kd;
+					rnat = r.rev_nat;
+					slave = r.slave;
+				}
+			}
+			if (lbr > 0) {
+				/* lb4_xlate / lb6_xlate: the L4 checksum field of
+				 * csum_l4_offset_and_flags; IPv4 patches it when the offset is
+				 * not 0, IPv6 whenever it reaches here (`if (csum_off)`) */
+				const uint32_t coff = t.proto == 6u ? 16u : t.proto == 17u ? 6u : t.proto == 58u ? 2u : 0u;
+				const bool l4c = !v4 || coff != 0u;
+				const uint32_t p = l4 + coff;
+				/* lb4_xlate: `if (new_saddr && *new_saddr)` */
+				const bool snat = loop && nsa != 0u;
+				const bool pchg = tu && (s.lb_flags & CGPU_LB_L4) && nport && kdf != nport;
+				const int32_t r = l4c ? fchk(p, 2, len, cap, DROP_CSUM_L4) : 0;
+				if (r) {
+					lbr = r;
+					rnat = slave = 0;
+				} else {
+					uint32_t D = 0;
+					if (v4) {
+						D = csum_add32(csum_add32(0u, ~t.da.x), nda.x);
+						if (snat)
+							D = csum_add32(csum_add32(D, ~t.sa.x), nsa);
+					} else {
+						D = csum_add32(D, ~t.da.x);
+						D = csum_add32(D, ~t.da.y);
+						D = csum_add32(D, ~t.da.z);
+						D = csum_add32(D, ~t.da.w);
+						D = csum_add32(D, nda.x);
+						D = csum_add32(D, nda.y);
+						D = csum_add32(D, nda.z);
+						D = csum_add32(D, nda.w);
+					}
+					if (RW) {
+						const bool pw = inwin && p < 64u; /* the field lies in the window */
+						uint32_t c = 0;
+						if (l4c)
+							c = pw ? fwin_get16(W, p) : (uint32_t) * reinterpret_cast<const uint16_t *>(f + p);
+						const uint32_t c1 = csum_l4_xlate(c, D, true, pchg, kdf, nport, t.proto == 17u);
+						const uint32_t h3 = csum_fold_not(csum_add32(D, ~W.h(24)));
+						if (inwin) {
+							if (v4) {
+								W.w[7] = (W.w[7] & 0xFFFFu) | (nda.x << 16);
+								W.w[8] = (W.w[8] & 0xFFFF0000u) | (nda.x >> 16);
+								if (snat) {
+									W.w[6] = (W.w[6] & 0xFFFFu) | (nsa << 16);
+									W.w[7] = (W.w[7] & 0xFFFF0000u) | (nsa >> 16);
+								}
+								W.w[6] = (W.w[6] & 0xFFFF0000u) | h3;
+							} else {
+								W.w[9] = (W.w[9] & 0xFFFFu) | (nda.x << 16);
+								W.w[10] = (nda.x >> 16) | (nda.y << 16);
+								W.w[11] = (nda.y >> 16) | (nda.z << 16);
+								W.w[12] = (nda.z >> 16) | (nda.w << 16);
+								W.w[13] = (W.w[13] & 0xFFFF0000u) | (nda.w >> 16);
+							}
+							if (l4c && pw)
+								fwin_put16(W, p, c1);
+							if (pchg)
+								fwin_put16(W, l4 + 2u, nport);
+							if (v4)
+								st_x4<false>(f + 16, W.w[4], W.w[5], W.w[6], W.w[7]);
+							st_x4<false>(f + 32, W.w[8], W.w[9], W.w[10], W.w[11]);
+							if (!v4 || t.proto == 6u)
+								st_x4<false>(f + 48, W.w[12], W.w[13], W.w[14], W.w[15]);
+							if (l4c && !pw)
+								st_h(f + p, c1);
+						} else {
+							if (v4) {
+								st_h(f + 30, nda.x & 0xFFFFu);
+								st_h(f + 32, nda.x >> 16);
+								if (snat) {
+									st_h(f + 26, nsa & 0xFFFFu);
+									st_h(f + 28, nsa >> 16);
+								}
+								st_h(f + 24, h3);
+							} else {
+								const uint32_t d[4] = {nda.x, nda.y, nda.z, nda.w};
+#pragma unroll
+								for (int k = 0; k < 4; k++) {
+									st_h(f + 38 + 4 * k, d[k] & 0xFFFFu);
+									st_h(f + 40 + 4 * k, d[k] >> 16);
+								}
+							}
+							if (l4c)
+								st_h(f + p, c1);
+							if (pchg)
+								st_h(f + l4 + 2u, nport);
+						}
+					}
+					/* tuple.daddr: the service address is kept on loopback */
+					if (!loop)
+						t.da = nda;
+					if (loop)
+						t.sa.x = nsa;
+					pdone = pchg;
+					pnew = nport;
+				}
+			}
+			if (lbr < 0)
+				st_lb = 1u;
+		}
+		int32_t v;
+		uint32_t id = 0, st;
+		if (st_lb) {
+			/* the step's drop: DROP_NO_SERVICE at stage 6 as cgpu_classify_v4_lb,
+			 * a checksum field out of reach at stage 5 */
+			v = lbr;
+			st = lbr == DROP_NO_SERVICE ? 6u : 5u;
+		} else {
+			if (t.status == 0) {
+				parse_frame_post(s, W, f, t, l4, inwin, len, cap);
+				/* ct_lookup reloads the dport from the packet as rewritten */
+				if (t.status == 0 && s.ct_proto_gate && pdone)
+					t.dport = pnew;
+			}
+			if (t.status == 0) {
+				const decision d = v4
+					? decide<0>(s, egress, t.frag, t.sa.x, t.da.x, uint4{}, uint4{}, t.dport, t.proto, ep)
+					: decide<1>(s, egress, false, 0u, 0u, t.sa, t.da, t.dport, t.proto, ep);
+				v = d.v;
+				id = d.id;
+				st = d.st;
+				if (d.ctr >= 0) {
+					const uint32_t c = (uint32_t)d.ctr;
+					if (c < s.hot_slots && len < PK_MAX_LEN) {
+						atomicAdd((unsigned long long *)&lctr[c],
+							  (1ull << PK_SHIFT) | (unsigned long long)len);
+					} else if (len < PKC_MAX_LEN) {
+						atomicAdd((unsigned long long *)&a.pk[c],
+							  (1ull << PKC_SHIFT) | (unsigned long long)len);
+					} else {
+						atomicAdd((unsigned long long *)&a.delta[2u * c], 1ull);
+						atomicAdd((unsigned long long *)&a.delta[2u * c + 1u], (unsigned long long)len);
+					}
+				}
+			} else if (t.status == FRAME_NOT_CLASSIFIED) {
+				v = 0;
+				st = CGPU_STAGE_NOT_CLASSIFIED;
+			} else {
+				v = t.status;
+				st = v == DROP_CT_UNKNOWN_PROTO ? 4u : 5u;
+			}
+		}
+		a.verdict[i] = v;
+		a.identity[i] = id;
+		if (a.stage)
+			a.stage[i] = (uint8_t)st;
+		if (a.lb_ret)
+			a.lb_ret[i] = lbr;
+		if (a.rev_nat)
+			a.rev_nat[i] = (uint16_t)rnat;
+		if (a.slave)
+			a.slave[i] = (uint16_t)slave;
+		if (st == CGPU_STAGE_NOT_CLASSIFIED || v == DROP_SNAPLEN || v > 0)
+			continue;
+		const uint32_t reason = v < 0 ? (uint32_t)(-v) & 0xffu : 0u;
+		const uint32_t dir = egress ? 1u : 0u;
+		const int b = reason == 0u ? 0 : reason == 133u ? 1 : reason == 137u ? 2 : -1;
+		if (b < 0) {
+			const uint32_t key = (reason * 4u + dir + 1u) * 2u;
+			atomicAdd((unsigned long long *)&met[key], 1ull);
+			atomicAdd((unsigned long long *)&met[key + 1], (unsigned long long)len);
+		} else {
+#pragma unroll
+			for (int k = 0; k < 6; k++) {
+				const bool hit = k == 2 * b + (int)dir;
+				mcnt[k] += hit ? 1u : 0u;
+				mbyt[k] += hit ? len : 0u;
+			}
+		}
+	}
+	const uint32_t reasons[3] = {0u, 133u, 137u};
+#pragma unroll
+	for (int k = 0; k < 6; k++) {
+		const uint64_t c = wave_sum(mcnt[k]);
+		const uint64_t b = wave_sum(mbyt[k]);
+		if ((threadIdx.x & 63) == 0 && c) {
+			const uint32_t key = (reasons[k >> 1] * 4u + ((k & 1) ? 2u : 1u)) * 2u;
+			atomicAdd((unsigned long long *)&met[key], (unsigned long long)c);
+			atomicAdd((unsigned long long *)&met[key + 1], (unsigned long long)b);
+		}
+	}
+	__syncthreads();
+	for (uint32_t k = threadIdx.x; k < s.hot_slots; k += NT) {
+		const uint64_t v = lctr[k];
+		if (v) {
+			atomicAdd((unsigned long long *)&a.delta[2u * k], v >> PK_SHIFT);
+			atomicAdd((unsigned long long *)&a.delta[2u * k + 1u], v & PK_BYTES_MASK);
+		}
+	}
+}
+
 /* Q consecutive elements of a 1 / 2 / 4-byte column from one nontemporal
  * load of Q * sizeof(T) bytes (p aligned to that), and the store of Q */
 template <int Q, typename T> __device__ __forceinline__ void ld_colq(const T *p, uint32_t (&v)[Q])
@@ -5415,6 +6008,47 @@ hipError_t launch_classify_frames(const cgpu_snapshot &s0, const frames_args &a,
 			c.stage += off;
 		const unsigned g = (unsigned)std::min<uint64_t>((m + NT - 1) / NT, cap);
 		hipLaunchKernelGGL((k_frames<1, NT>), dim3(g), dim3(NT), lds, st, s, c);
+		if (s.cold_hi) {
+			const unsigned ug = std::min<unsigned>((s.cold_hi + 255) / 256, 1024);
+			hipLaunchKernelGGL(k_unpack, dim3(ug), dim3(256), 0, st, a.delta, a.pk, 0u, s.cold_hi);
+		}
+	}
+	return hipGetLastError();
+}
+
+/* launch_classify_frames' grid, chunks and unpack for k_frames_lb */
+hipError_t launch_classify_frames_lb(const cgpu_snapshot &s0, const frames_lb_args &a, hipStream_t st)
+{
+	constexpr int NT = 1024;
+	const cgpu_snapshot s = with_lds_hot(s0, X4_LDS_BUDGET / 8u);
+	const size_t lds = (size_t)s.hot_slots * 8u;
+	const uint64_t cap = 2ull * 256ull;
+	const uint64_t per_launch = std::min<uint64_t>(cap * (1ull << 22), PKC_CHUNK);
+	for (uint64_t off = 0; off < a.n; off += per_launch) {
+		frames_lb_args c = a;
+		const uint64_t m = std::min<uint64_t>(a.n - off, per_launch);
+		c.n = m;
+		c.data += off * a.stride;
+		c.len += off;
+		c.flags += off;
+		c.ep += off;
+		if (c.hash)
+			c.hash += off;
+		c.verdict += off;
+		c.identity += off;
+		if (c.stage)
+			c.stage += off;
+		if (c.lb_ret)
+			c.lb_ret += off;
+		if (c.rev_nat)
+			c.rev_nat += off;
+		if (c.slave)
+			c.slave += off;
+		const unsigned g = (unsigned)std::min<uint64_t>((m + NT - 1) / NT, cap);
+		if (a.rewrite)
+			hipLaunchKernelGGL((k_frames_lb<true, NT>), dim3(g), dim3(NT), lds, st, s, c);
+		else
+			hipLaunchKernelGGL((k_frames_lb<false, NT>), dim3(g), dim3(NT), lds, st, s, c);
 		if (s.cold_hi) {
 			const unsigned ug = std::min<unsigned>((s.cold_hi + 255) / 256, 1024);
 			hipLaunchKernelGGL(k_unpack, dim3(ug), dim3(256), 0, st, a.delta, a.pk, 0u, s.cold_hi);

@@ -229,6 +229,26 @@ hipError_t launch_classify_frames_x4(const cgpu_snapshot &s, const frames_args &
 				     hipStream_t st);
 hipError_t launch_classify_frames(const cgpu_snapshot &s, const frames_args &a, hipStream_t st);
 
+/* the service step on raw frames (cgpu_classify_frames_lb): the columns of
+ * cgpu_flb_in, the classify outputs and those of cgpu_flb_out */
+struct frames_lb_args {
+	uint8_t *data;
+	const uint32_t *len;
+	const uint8_t *flags;
+	const uint16_t *ep;
+	const uint32_t *hash; /* NULL: cgpu_flow_hash / _hash6 of the frame's fields */
+	uint32_t stride, rewrite;
+	uint64_t n;
+	int32_t *verdict;
+	uint32_t *identity;
+	uint8_t *stage;
+	int32_t *lb_ret;
+	uint16_t *rev_nat, *slave;
+	uint64_t *delta;
+	uint64_t *pk;
+};
+hipError_t launch_classify_frames_lb(const cgpu_snapshot &s, const frames_lb_args &a, hipStream_t st);
+
 /* stateful classification (cgpu_classify_v4_ct): packet columns, outputs,
  * and the caller-allocated scratch (ct_scratch_layout in host.cpp) */
 struct ct_launch {

@@ -25,7 +25,8 @@ import ipaddress
 import numpy as np
 
 from . import layouts as L
-from ._abi import (CgpuConfig, CgpuError, CtlbOut, DlvIn, DlvOut, FrameTuples, Frames, FwdIn, FwdOut, FwdParams,
+from ._abi import (CgpuConfig, CgpuError, CtlbOut, DlvIn, DlvOut, FlbIn, FlbOut, FrameTuples, Frames, FwdIn, FwdOut,
+                   FwdParams,
                    FwdfIn, FwdfParams, Lb4Out, Lb4Tuples, Rnat4Out, Rnat6Out, TuplesV4, TuplesV4Ct, TuplesV6Ct,
                    TuplesV6, check, lib)
 
@@ -1142,13 +1143,18 @@ class Engine:
     _FWDF_KEYS = _FWD_KEYS + ("host_mac", "rewrite")
 
     def classify_frames(self, f: dict, out: dict | None = None, stage: bool = True, stream=None,
-                        forward: dict | None = None):
+                        forward: dict | None = None, lb: dict | None = None):
         """Raw frames to verdicts in one pass (cgpu_classify_frames).
+        lb=<dict of classify_frames_lb's hash / rewrite>: the egress service
+        step first (cgpu_classify_frames_lb; out["lb_ret" / "rev_nat" /
+        "slave"] too), which with rewrite (the default) translates f["data"]
+        in place; None is the call without the step.
         forward=<forward_frames' keyword parameters mode, encap, ipv4_mask,
         host_ifindex, encap_ifindex, host_mac, rewrite>: then the forwarding
-        step on the frames with the call's own verdict and stage and no
-        tunnel column, into out["fwd_action" / "fwd_ret" / "fwd_ifindex" /
-        "fwd_arg"]; with rewrite (the default) f["data"] is modified in place."""
+        step on the frames (as translated) with the call's own verdict and
+        stage and no tunnel column, into out["fwd_action" / "fwd_ret" /
+        "fwd_ifindex" / "fwd_arg"]; with rewrite (the default) f["data"] is
+        modified in place."""
         import torch
         n = f["len"].numel()
         dev = f["len"].device
@@ -1158,20 +1164,54 @@ class Engine:
                 raise TypeError(f"unknown forward parameter(s) {sorted(bad)}")
             if not stage and forward.get("mode", L.FWD_LXC) == L.FWD_LXC:
                 raise ValueError("forward= in FWD_LXC mode reads the stage output")
-        if out is None:
-            out = {"verdict": torch.empty(n, dtype=torch.int32, device=dev),
-                   "identity": torch.empty(n, dtype=torch.int32, device=dev),
-                   "stage": torch.empty(n, dtype=torch.uint8, device=dev) if stage else None}
-        fr = self._frames(f)
-        check(self.L.cgpu_classify_frames(self.h, C.byref(fr), n, _ptr(out["verdict"]),
-                                          _ptr(out["identity"]), _ptr(out.get("stage")),
-                                          _stream(stream)), "cgpu_classify_frames")
+        if lb is not None:
+            bad = set(lb) - {"hash", "rewrite"}
+            if bad:
+                raise TypeError(f"unknown lb parameter(s) {sorted(bad)}")
+            out = self.classify_frames_lb(f, out=out, stage=stage, stream=stream, **lb)
+        else:
+            if out is None:
+                out = {"verdict": torch.empty(n, dtype=torch.int32, device=dev),
+                       "identity": torch.empty(n, dtype=torch.int32, device=dev),
+                       "stage": torch.empty(n, dtype=torch.uint8, device=dev) if stage else None}
+            fr = self._frames(f)
+            check(self.L.cgpu_classify_frames(self.h, C.byref(fr), n, _ptr(out["verdict"]),
+                                              _ptr(out["identity"]), _ptr(out.get("stage")),
+                                              _stream(stream)), "cgpu_classify_frames")
         if forward is not None:
             given = {k: out.get("fwd_" + k) for k in ("action", "ret", "ifindex", "arg")}
             r = self.forward_frames(f, verdict=out["verdict"], stage=out.get("stage"),
                                     out=given if given["action"] is not None else None, stream=stream, **forward)
             for k, v in r.items():
                 out["fwd_" + k] = v
+        return out
+
+    def classify_frames_lb(self, f: dict, hash=None, rewrite: bool = True, out: dict | None = None,
+                           stage: bool = True, stream=None):
+        """cgpu_classify_frames_lb: classify_frames with the stateless egress
+        service step on the frame's own fields and, with `rewrite`, the bytes
+        lb4_xlate / lb6_xlate store (daddr, the loopback saddr, dport, the
+        IPv4 header checksum and the L4 checksum) in f["data"] itself
+        (include/cgpu.h has the rules).  hash: the int32 view of skb->hash per
+        frame, or None for flow_hash / flow_hash6 of the frame's fields.
+        Returns verdict, identity, stage, lb_ret, rev_nat, slave."""
+        import torch
+        data = f["data"]
+        assert data.dim() == 2 and data.is_contiguous()
+        n = f["len"].numel()
+        dev = data.device
+        if out is None:
+            out = {}
+        for k, dt in (("verdict", torch.int32), ("identity", torch.int32), ("stage", torch.uint8),
+                      ("lb_ret", torch.int32), ("rev_nat", torch.int16), ("slave", torch.int16)):
+            if k not in out:
+                out[k] = torch.empty(n, dtype=dt, device=dev) if (stage or k != "stage") else None
+        iv = FlbIn(data.data_ptr(), f["len"].data_ptr(), f["flags"].data_ptr(), f["ep"].data_ptr(),
+                   data.shape[1], 0, _ptr(hash))
+        ov = FlbOut(_ptr(out.get("lb_ret")), _ptr(out.get("rev_nat")), _ptr(out.get("slave")))
+        check(self.L.cgpu_classify_frames_lb(self.h, C.byref(iv), L.FLB_REWRITE if rewrite else 0, n,
+                                             _ptr(out["verdict"]), _ptr(out["identity"]), _ptr(out.get("stage")),
+                                             C.byref(ov), _stream(stream)), "cgpu_classify_frames_lb")
         return out
 
     def forward_frames(self, f: dict, verdict=None, stage=None, tunnel=None, mode=L.FWD_LXC, encap=True,

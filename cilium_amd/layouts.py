@@ -253,6 +253,8 @@ ENDPOINT_F_HOST = 1
 FWD_LXC, FWD_NETDEV = 0, 1
 FWD_ENCAP = 1
 FWDF_REWRITE = 1  # cgpu_forward_frames: rewrite MACs, ttl / hop limit and IPv4 checksum in place
+FLB_REWRITE = 1   # cgpu_classify_frames_lb: store the service step's daddr / saddr / dport and checksums
+DROP_WRITE_ERROR, DROP_CSUM_L4 = -141, -154
 FWD_NONE, FWD_DROP, FWD_PROXY, FWD_LOCAL, FWD_HOST, FWD_OVERLAY, FWD_STACK, FWD_TIME_EXCEEDED = range(8)
 DROP_INVALID = -134
 TUNNEL_ENDPOINT_MAP_SIZE = 65536  # bpf/node_config.h:54

@@ -890,6 +890,104 @@ int cgpu_classify_frames(cgpu_ctx *ctx, const cgpu_frames *f, size_t n, int32_t 
 int cgpu_classify_frames_host(cgpu_ctx *ctx, const cgpu_frames *f, size_t n, int32_t *verdict,
 			      uint32_t *identity, uint8_t *stage, void *stream);
 
+/*
+ * cgpu_classify_frames with the egress service step (the stateless one of
+ * cgpu_classify_v4_lb / _v6_lb: CGPU_LB_* ret codes and cgpu_flow_hash are
+ * declared further down) and, with CGPU_FLB_REWRITE, what that step writes
+ * into the packet: handle_ipv4_from_lxc / ipv6_l3_from_lxc from the Ethernet
+ * header to ct_lookup (bpf_lxc.c:426-481, :82-163), with lb4_xlate / lb6_xlate
+ * (lib/lb.h:653-697, :398-424), l4_modify_port (lib/l4.h:50-60) and
+ * lib/csum.h.  Per frame, in the reference's order:
+ *
+ *   a. cgpu_frames_parse's steps up to and including extract_l4_port, with
+ *      its statuses and its CGPU_DROP_SNAPLEN rule.  A frame that ends here,
+ *      and every ingress frame, gets cgpu_classify_frames' result; lb_ret 0.
+ *   b. The decision of the stateless service step on the frame's own fields:
+ *      the key dport is the u16 at l4 + 2 for TCP / UDP under CGPU_LB_L4,
+ *      else 0; other protocols than TCP / UDP / ICMP / ICMPv6 skip the step
+ *      under CGPU_LB_L4.  The hash is hash[i], or without a hash column
+ *      cgpu_flow_hash / cgpu_flow_hash6 over (saddr, daddr, sport, key dport,
+ *      proto) before translation, sport = the u16 at l4 for TCP / UDP when it
+ *      lies within min(len, stride), else 0.  DROP_NO_SERVICE: verdict -158,
+ *      identity 0, stage 6, metrics {158, egress}; the frame is untouched.
+ *   c. The rewrite of a translated frame.  With c a checksum field as loaded
+ *      (little-endian load of the wire bytes, as every word below),
+ *      add(a, b) = (r = a + b, r + (r < b)) in u32 and fold(t) = two rounds of
+ *      t = (t & 0xffff) + (t >> 16):
+ *        D   = csum_diff: from 0 (IPv4 loopback: from the daddr's D), add(D,
+ *              ~w) for every old word, then add(D, w) for every new word;
+ *        l3_csum_replace(off, 0, D, 0), l4_csum_replace(off, 0, D, PSEUDO_HDR):
+ *              c' = (u16)~fold(add(D, ~(u32)c));
+ *        l4_csum_replace(off, from, to, 2):
+ *              c' = (u16)~fold(add(add(~(u32)c, ~(u32)from), to));
+ *        UDP (BPF_F_MARK_MANGLED_0): a field of 0 stays 0 through every
+ *              patch, a patch that yields 0 stores 0xFFFF.
+ *      IPv4: daddr to bytes 30..33; on loopback IPV4_LOOPBACK to the saddr at
+ *      26..29; the header checksum at 24..25 patched by D; the L4 checksum of
+ *      csum_l4_offset_and_flags (TCP l4 + 16, UDP l4 + 6, protocol 58 l4 + 2;
+ *      ICMP and the rest have none) patched by the same D.
+ *      IPv6: daddr to bytes 38..53; the L4 checksum (TCP l4 + 16, UDP l4 + 6,
+ *      ICMPv6 l4 + 2) patched by the 16-byte D.  lb6_xlate tests `if
+ *      (csum_off)`, the pointer: any other next header that reaches it has
+ *      the two bytes at l4 + 0 patched.
+ *      Both: svc->port && key.dport != svc->port on TCP / UDP under
+ *      CGPU_LB_L4 patches the L4 checksum for the port (from = key.dport) and
+ *      stores the port at l4 + 2.  key.dport is the key's as the lookups left
+ *      it: lb{4,6}_lookup_service set it to 0 before they try the L3 key
+ *      (lib/lb.h:617, :363), so behind an L3 frontend whose backend carries a
+ *      port the patch starts from 0 and not from the packet's port, as in the
+ *      reference; the checksum of such a frame does not verify afterwards.
+ *      An L4 checksum field past len: CGPU_DROP_CSUM_L4, verdict = that code,
+ *      identity 0, stage 5, metrics {154, egress}; inside len but past the
+ *      stored slot: CGPU_DROP_SNAPLEN, not counted.  A frame dropped in (b) or
+ *      here keeps every byte; drop codes are decided with or without
+ *      CGPU_FLB_REWRITE.  Every store lies within len once (a) has passed
+ *      (extract_l4_port has loaded the dport), so CGPU_DROP_WRITE_ERROR is
+ *      defined and never returned.  A translated frame stays rewritten
+ *      whatever a later stage decides.
+ *   d. cgpu_frames_parse's remaining steps (ct_lookup's port extraction and
+ *      protocol gate) with the dport as rewritten.
+ *   e. The cgpu_classify_v4 / _v6 decision on (saddr after the step,
+ *      tuple.daddr, that dport, proto); on loopback tuple.daddr keeps the
+ *      service address.  Counters and metrics as cgpu_classify_v4_lb / _v6_lb
+ *      of that tuple.
+ *
+ * The frame is taken as carrying full checksums (ip_summed is not
+ * CHECKSUM_PARTIAL).  Every new value is computed from the frame as it came
+ * and the stores follow in the reference's order; the two differ from the
+ * reference only for an IPv4 header with ihl < 5, whose L4 header overlaps
+ * the IP header.  Not in scope: the stateful (_ctlb) form on frames, reverse
+ * NAT on frames, a _host form, bpf_lb.c's netdev mode, and skb->csum /
+ * CHECKSUM_COMPLETE bookkeeping.
+ *
+ * -EINVAL, judged before the context, for a null struct or a null required
+ * column (data, len, flags, ep, verdict, identity), unknown flag bits, a
+ * nonzero reserved, a misaligned 2- or 4-byte column, a stride that is not a
+ * multiple of 16 or is below 64, or data that is not 16-byte aligned; -ENODEV
+ * on a host-only context; n == 0 is a no-op.  One snapshot serves the batch.
+ */
+#define CGPU_FLB_REWRITE 1u
+#define CGPU_DROP_WRITE_ERROR (-141) /* DROP_WRITE_ERROR, bpf/lib/common.h */
+#define CGPU_DROP_CSUM_L4 (-154)     /* DROP_CSUM_L4 */
+
+typedef struct cgpu_flb_in { /* device pointers; the slots of cgpu_frames, same stride / alignment rules */
+	uint8_t *data;             /* written only with CGPU_FLB_REWRITE */
+	const uint32_t *len;
+	const uint8_t *flags;      /* CGPU_F_EGRESS */
+	const uint16_t *ep;
+	uint32_t stride, reserved; /* reserved must be 0 */
+	const uint32_t *hash;      /* skb->hash per frame, or NULL (above) */
+} cgpu_flb_in;
+
+typedef struct cgpu_flb_out { /* device pointers; each may be NULL; every element of a given column is written */
+	int32_t *lb_ret;           /* CGPU_LB_NONE / CGPU_LB_XLATED / CGPU_LB_XLATED_LOOPBACK, or the drop of the step */
+	uint16_t *rev_nat, *slave; /* the chosen entry's, 0 where not translated */
+} cgpu_flb_out;
+
+int cgpu_classify_frames_lb(cgpu_ctx *ctx, const cgpu_flb_in *in, uint32_t flags, size_t n,
+			    int32_t *verdict, uint32_t *identity, uint8_t *stage,
+			    const cgpu_flb_out *lb /* may be NULL */, void *stream);
+
 /* ------------------------------------------------------------------ */
 /* conntrack: the map cilium_ct4_global               */
 /* ------------------------------------------------------------------ */
