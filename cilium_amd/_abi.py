@@ -78,6 +78,16 @@ class Rnat6Out(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("saddr", "sport", "applied")]
 
 
+class Rnf4In(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("len", C.c_void_p), ("stride", C.c_uint32), ("reserved", C.c_uint32),
+                ("applied", C.c_void_p), ("saddr", C.c_void_p), ("daddr", C.c_void_p), ("sport", C.c_void_p)]
+
+
+class Rnf6In(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("len", C.c_void_p), ("stride", C.c_uint32), ("reserved", C.c_uint32),
+                ("applied", C.c_void_p), ("saddr", C.c_void_p), ("sport", C.c_void_p)]
+
+
 class FwdParams(C.Structure):
     _fields_ = [("mode", C.c_uint32), ("flags", C.c_uint32), ("ipv4_mask", C.c_uint32),
                 ("host_ifindex", C.c_uint32), ("encap_ifindex", C.c_uint32),
@@ -266,7 +276,9 @@ PROTOS = {
                                        C.POINTER(Rnat6Out), vp]),
     "cgpu_classify_v6_ctlb_rnat": (i32, [vp, C.POINTER(TuplesV6Ct), vp, sz, u32, C.POINTER(CtlbOut),
                                          C.POINTER(Rnat6Out), vp]),
-    "cgpu_l3_compile": (i32, [vp, vp, vp, vp, u32, vp]),
+    "cgpu_rnat_frames_v4": (i32, [vp, C.POINTER(Rnf4In), u32, sz, vp, vp]),
+    "cgpu_rnat_frames_v6": (i32, [vp, C.POINTER(Rnf6In), u32, sz, vp, vp]),
+    "cgpu_l3_compile":(i32, [vp, vp, vp, vp, u32, vp]),
     "cgpu_mapstate_sync": (i32, [vp, vp, vp, vp, vp, vp]),
     "cgpu_counter_delta_bytes": (sz, [vp]),
     "cgpu_counter_bind": (i32, [vp, vp, sz]),

@@ -6265,6 +6265,74 @@ CGPU_EXPORT int cgpu_classify_frames_lb(cgpu_ctx *c, const cgpu_flb_in *in, uint
 	return 0;
 }
 
+/* reverse NAT on raw frames (cgpu.h cgpu_rnat_frames_v4 / _v6): judged before
+ * the context as cgpu_classify_frames_lb is; the step reads no table, so no
+ * snapshot is pinned */
+static_assert(sizeof(cgpu_rnf4_in) == 56 && offsetof(cgpu_rnf4_in, applied) == 24, "cgpu_rnf4_in layout");
+static_assert(sizeof(cgpu_rnf6_in) == 48 && offsetof(cgpu_rnf6_in, sport) == 40, "cgpu_rnf6_in layout");
+static int rnat_frames(cgpu_ctx *c, rnat_frames_args a, uint32_t reserved, uint32_t flags, void *stream)
+{
+	if ((flags & ~CGPU_RNF_REWRITE) || reserved)
+		return fail(-EINVAL, "unknown flags 0x%x or nonzero reserved", flags);
+	if (a.stride < 64 || (a.stride & 15))
+		return fail(-EINVAL, "frame stride must be a multiple of 16 and >= 64");
+	if ((uintptr_t)a.data & 15)
+		return fail(-EINVAL, "frame buffer must be 16-byte aligned");
+	if (a.n && (!a.data || !a.len || !a.applied || !a.saddr || !a.sport || (!a.v6 && !a.daddr)))
+		return fail(-EINVAL, "null data, len, applied, saddr, daddr or sport column");
+	if ((uintptr_t)a.saddr & (a.v6 ? 15u : 3u))
+		return fail(-EINVAL, a.v6 ? "saddr rows not 16-byte aligned" : "4-byte column not 4-byte aligned");
+	if (((uintptr_t)a.len | (uintptr_t)a.daddr | (uintptr_t)a.ret) & 3u)
+		return fail(-EINVAL, "4-byte column not 4-byte aligned");
+	if ((uintptr_t)a.sport & 1u)
+		return fail(-EINVAL, "2-byte column not 2-byte aligned");
+	if (!a.n)
+		return 0;
+	if (c->device < 0)
+		return fail(-ENODEV, "context has no device (host-only); no CPU path");
+	a.rewrite = flags & CGPU_RNF_REWRITE;
+	HIP_OR_EIO(hipSetDevice(c->device));
+	HIP_OR_EIO(launch_rnat_frames(a, (hipStream_t)stream));
+	return 0;
+}
+
+CGPU_EXPORT int cgpu_rnat_frames_v4(cgpu_ctx *c, const cgpu_rnf4_in *in, uint32_t flags, size_t n, int32_t *ret,
+				    void *stream)
+{
+	if (!c || !in)
+		return fail(-EINVAL, "null argument");
+	rnat_frames_args a{};
+	a.data = in->data;
+	a.len = in->len;
+	a.applied = in->applied;
+	a.saddr = in->saddr;
+	a.daddr = in->daddr;
+	a.sport = in->sport;
+	a.ret = ret;
+	a.stride = in->stride;
+	a.n = n;
+	a.v6 = 0;
+	return rnat_frames(c, a, in->reserved, flags, stream);
+}
+
+CGPU_EXPORT int cgpu_rnat_frames_v6(cgpu_ctx *c, const cgpu_rnf6_in *in, uint32_t flags, size_t n, int32_t *ret,
+				    void *stream)
+{
+	if (!c || !in)
+		return fail(-EINVAL, "null argument");
+	rnat_frames_args a{};
+	a.data = in->data;
+	a.len = in->len;
+	a.applied = in->applied;
+	a.saddr = in->saddr;
+	a.sport = in->sport;
+	a.ret = ret;
+	a.stride = in->stride;
+	a.n = n;
+	a.v6 = 1;
+	return rnat_frames(c, a, in->reserved, flags, stream);
+}
+
 CGPU_EXPORT int cgpu_classify_frames_host(cgpu_ctx *c, const cgpu_frames *f, size_t n, int32_t *verdict,
 					  uint32_t *identity, uint8_t *stage, void *stream)
 {

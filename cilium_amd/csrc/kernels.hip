@@ -4862,6 +4862,203 @@ __global__ __launch_bounds__(NT) void k_frames_lb(cgpu_snapshot s, frames_lb_arg
 	}
 }
 
+/* ------------------------------------------------------------------ */
+/* reverse NAT on raw frames (cgpu_rnat_frames_v4 / _v6)                */
+/* ------------------------------------------------------------------ */
+/* ipv6_hdrlen as the parse walks it (parse_frame_w): 0 and the L4 protocol /
+ * the header length behind the Ethernet header, or the parse's status.  A
+ * copy beside the parse's walk, as parse_frame_pre's is: the frames kernels
+ * stay as they compile today.  A change of the walk goes into all three. */
+__device__ __forceinline__ int32_t ipv6_walk(const uint8_t *f, uint32_t len, uint32_t cap, uint32_t &nh,
+					     uint32_t &off)
+{
+	int32_t r = 1;
+	off = 40u;
+	for (int k = 0; k < 4 && r == 1; k++) {
+		if (nh == 59u) {
+			r = DROP_INVALID_EXTHDR;
+		} else if (nh == 44u) {
+			r = DROP_FRAG_NOSUPPORT;
+		} else if (nh == 0u || nh == 43u || nh == 51u || nh == 60u) {
+			const uint32_t o = 14u + off;
+			r = fchk(o, 2, len, cap, DROP_INVALID);
+			if (!r) {
+				const uint32_t hl = f[o + 1];
+				nh = f[o];
+				off += nh == 51u ? (hl + 2u) << 2 : (hl + 1u) << 3;
+				r = 1;
+			}
+		} else {
+			r = 0;
+		}
+	}
+	return r == 1 ? DROP_INVALID_EXTHDR : r;
+}
+
+__device__ __forceinline__ uint32_t ld_h(const uint8_t *p) { return *reinterpret_cast<const uint16_t *>(p); }
+
+/* cgpu_rnat_frames_v4 / _v6 (cgpu.h has the rules): what __lb4_rev_nat /
+ * __lb6_rev_nat write into the packet, from the columns k_ct_rnat left.  One
+ * frame per lane in batch order, grid-stride.  The step has no gathers and
+ * only the applied frames (service replies) need their slot: a lane reads
+ * applied[i] first, and with 0 stores its ret and touches nothing else --
+ * not the slot, not the three rn columns.  An applied lane loads the slot's
+ * first 64 bytes as parse_frame does, computes every new value from the frame
+ * as it came, and stores only the 16-byte words of bytes 16..63 that changed
+ * (an option-less IPv4 / extension-less IPv6 frame; the TCP checksum of such
+ * an IPv6 frame at byte 70 goes by a halfword store); a frame with IPv4
+ * options or IPv6 extension headers stores halfwords in the reference's
+ * order, as k_frames_lb does. */
+template <bool V6, bool RW> __global__ __launch_bounds__(BLOCK) void k_rnat_frames(rnat_frames_args a)
+{
+	const uint64_t gstride = (uint64_t)gridDim.x * BLOCK;
+	for (uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i < a.n; i += gstride) {
+		int32_t ret = 0;
+		if (ntl(a.applied + i)) {
+			uint8_t *f = a.data + i * (uint64_t)a.stride;
+			fwin W;
+#pragma unroll
+			for (int k = 0; k < 4; k++) {
+				const uint4 v = ld_x4<true>(f + 16 * k);
+				W.w[4 * k] = v.x;
+				W.w[4 * k + 1] = v.y;
+				W.w[4 * k + 2] = v.z;
+				W.w[4 * k + 3] = v.w;
+			}
+			const uint32_t len = ntl(a.len + i);
+			const uint32_t cap = min(len, a.stride);
+			bool go = W.h(12) == (V6 ? 0xDD86u : 0x0008u) && cap >= (V6 ? 54u : 34u);
+			uint32_t l4 = 0, proto = 0;
+			if (go) {
+				if (V6) {
+					uint32_t off;
+					proto = W.b(20);
+					go = ipv6_walk(f, len, cap, proto, off) == 0;
+					l4 = 14u + off;
+				} else {
+					proto = W.b(23);
+					l4 = 14u + 4u * (W.b(14) & 15u);
+				}
+			}
+			const bool tu = proto == 6u || proto == 17u;
+			const bool udp = proto == 17u;
+			/* ct_lookup's protocol gate, and its port load */
+			go = go && (tu || proto == (V6 ? 58u : 1u)) && (!tu || l4 + 2u <= cap);
+			if (go) {
+				const bool inwin = l4 == (V6 ? 54u : 34u);
+				const uint32_t coff = proto == 6u ? 16u : udp ? 6u : proto == 58u ? 2u : 0u;
+				const bool l4c = V6 || coff != 0u;
+				const uint32_t p = l4 + coff;
+				ret = l4c ? fchk(p, 2, len, cap, DROP_CSUM_L4) : 0;
+				if (RW && !ret) {
+					const bool pw = inwin && p < 64u; /* the field lies in the window */
+					const uint32_t nsp = ntl(a.sport + i);
+					const uint32_t osp = !tu ? nsp : inwin ? W.h(V6 ? 54 : 34) : ld_h(f + l4);
+					const bool pchg = nsp != osp;
+					uint32_t c = 0;
+					if (l4c)
+						c = pw ? fwin_get16(W, p) : ld_h(f + p);
+					/* 1. reverse_map_l4_port / l4_modify_port */
+					uint32_t c1 = c;
+					if (pchg && !(udp && !c1)) {
+						c1 = csum_fold_not(csum_add32(csum_add32(~c1, ~osp), nsp));
+						if (udp && !c1)
+							c1 = 0xFFFFu;
+					}
+					/* 2., 3. the addresses and their csum_diff */
+					uint32_t D = 0, nda = 0, h3 = 0;
+					uint4 nsa;
+					bool dchg = false;
+					if (V6) {
+						nsa = ld_x4<true>(static_cast<const uint8_t *>(a.saddr) + 16u * i);
+						D = csum_add32(D, ~W.d(22));
+						D = csum_add32(D, ~W.d(26));
+						D = csum_add32(D, ~W.d(30));
+						D = csum_add32(D, ~W.d(34));
+						D = csum_add32(D, nsa.x);
+						D = csum_add32(D, nsa.y);
+						D = csum_add32(D, nsa.z);
+						D = csum_add32(D, nsa.w);
+					} else {
+						nsa = make_uint4(ntl(static_cast<const uint32_t *>(a.saddr) + i), 0, 0, 0);
+						nda = ntl(a.daddr + i);
+						dchg = nda != W.d(30);
+						if (dchg)
+							D = csum_add32(csum_add32(0u, ~W.d(30)), nda);
+						D = csum_add32(csum_add32(D, ~W.d(26)), nsa.x);
+						/* 4. l3_csum_replace(.., 0, D, 0) */
+						h3 = csum_fold_not(csum_add32(D, ~W.h(24)));
+					}
+					/* 5. l4_csum_replace(.., 0, D, BPF_F_PSEUDO_HDR) */
+					uint32_t c2 = c1;
+					if (l4c && !(udp && !c2)) {
+						c2 = csum_fold_not(csum_add32(D, ~c2));
+						if (udp && !c2)
+							c2 = 0xFFFFu;
+					}
+					if (inwin) {
+						const fwin W0 = W;
+						if (V6) {
+							if (pchg)
+								W.w[13] = (W.w[13] & 0xFFFFu) | (nsp << 16);
+							W.w[5] = (W.w[5] & 0xFFFFu) | (nsa.x << 16);
+							W.w[6] = (nsa.x >> 16) | (nsa.y << 16);
+							W.w[7] = (nsa.y >> 16) | (nsa.z << 16);
+							W.w[8] = (nsa.z >> 16) | (nsa.w << 16);
+							W.w[9] = (W.w[9] & 0xFFFF0000u) | (nsa.w >> 16);
+						} else {
+							if (pchg)
+								W.w[8] = (W.w[8] & 0xFFFFu) | (nsp << 16);
+							if (dchg) {
+								W.w[7] = (W.w[7] & 0xFFFFu) | (nda << 16);
+								W.w[8] = (W.w[8] & 0xFFFF0000u) | (nda >> 16);
+							}
+							W.w[6] = (nsa.x << 16) | h3;
+							W.w[7] = (W.w[7] & 0xFFFF0000u) | (nsa.x >> 16);
+						}
+						if (l4c && pw)
+							fwin_put16(W, p, c2);
+#pragma unroll
+						for (int k = 1; k < 4; k++) {
+							if (W.w[4 * k] != W0.w[4 * k] || W.w[4 * k + 1] != W0.w[4 * k + 1] ||
+							    W.w[4 * k + 2] != W0.w[4 * k + 2] || W.w[4 * k + 3] != W0.w[4 * k + 3])
+								st_x4<false>(f + 16 * k, W.w[4 * k], W.w[4 * k + 1], W.w[4 * k + 2],
+									     W.w[4 * k + 3]);
+						}
+						if (l4c && !pw && c2 != c)
+							st_h(f + p, c2);
+					} else {
+						if (pchg) {
+							st_h(f + p, c1);
+							st_h(f + l4, nsp);
+						}
+						if (V6) {
+							const uint32_t d[4] = {nsa.x, nsa.y, nsa.z, nsa.w};
+#pragma unroll
+							for (int k = 0; k < 4; k++) {
+								st_h(f + 22 + 4 * k, d[k] & 0xFFFFu);
+								st_h(f + 24 + 4 * k, d[k] >> 16);
+							}
+						} else {
+							if (dchg) {
+								st_h(f + 30, nda & 0xFFFFu);
+								st_h(f + 32, nda >> 16);
+							}
+							st_h(f + 26, nsa.x & 0xFFFFu);
+							st_h(f + 28, nsa.x >> 16);
+							st_h(f + 24, h3);
+						}
+						if (l4c)
+							st_h(f + p, c2);
+					}
+				}
+			}
+		}
+		if (a.ret)
+			__builtin_nontemporal_store(ret, a.ret + i);
+	}
+}
+
 /* Q consecutive elements of a 1 / 2 / 4-byte column from one nontemporal
  * load of Q * sizeof(T) bytes (p aligned to that), and the store of Q */
 template <int Q, typename T> __device__ __forceinline__ void ld_colq(const T *p, uint32_t (&v)[Q])
@@ -6053,6 +6250,25 @@ hipError_t launch_classify_frames_lb(const cgpu_snapshot &s0, const frames_lb_ar
 			const unsigned ug = std::min<unsigned>((s.cold_hi + 255) / 256, 1024);
 			hipLaunchKernelGGL(k_unpack, dim3(ug), dim3(256), 0, st, a.delta, a.pk, 0u, s.cold_hi);
 		}
+	}
+	return hipGetLastError();
+}
+
+hipError_t launch_rnat_frames(const rnat_frames_args &a, hipStream_t st)
+{
+	if (!a.n)
+		return hipSuccess;
+	const dim3 g(grid_for(a.n)), b(BLOCK);
+	if (a.v6) {
+		if (a.rewrite)
+			hipLaunchKernelGGL((k_rnat_frames<true, true>), g, b, 0, st, a);
+		else
+			hipLaunchKernelGGL((k_rnat_frames<true, false>), g, b, 0, st, a);
+	} else {
+		if (a.rewrite)
+			hipLaunchKernelGGL((k_rnat_frames<false, true>), g, b, 0, st, a);
+		else
+			hipLaunchKernelGGL((k_rnat_frames<false, false>), g, b, 0, st, a);
 	}
 	return hipGetLastError();
 }

@@ -249,6 +249,22 @@ struct frames_lb_args {
 };
 hipError_t launch_classify_frames_lb(const cgpu_snapshot &s, const frames_lb_args &a, hipStream_t st);
 
+/* reverse NAT on raw frames (cgpu_rnat_frames_v4 / _v6): the columns of
+ * cgpu_rnf4_in / cgpu_rnf6_in (saddr: u32 per frame, or 16-byte rows) */
+struct rnat_frames_args {
+	uint8_t *data;
+	const uint32_t *len;
+	const uint8_t *applied;
+	const void *saddr;
+	const uint32_t *daddr; /* IPv4 */
+	const uint16_t *sport;
+	int32_t *ret;          /* may be NULL */
+	uint32_t stride, rewrite;
+	uint64_t n;
+	int v6;
+};
+hipError_t launch_rnat_frames(const rnat_frames_args &a, hipStream_t st);
+
 /* stateful classification (cgpu_classify_v4_ct): packet columns, outputs,
  * and the caller-allocated scratch (ct_scratch_layout in host.cpp) */
 struct ct_launch {

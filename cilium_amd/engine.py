@@ -27,7 +27,7 @@ import numpy as np
 from . import layouts as L
 from ._abi import (CgpuConfig, CgpuError, CtlbOut, DlvIn, DlvOut, FlbIn, FlbOut, FrameTuples, Frames, FwdIn, FwdOut,
                    FwdParams,
-                   FwdfIn, FwdfParams, Lb4Out, Lb4Tuples, Rnat4Out, Rnat6Out, TuplesV4, TuplesV4Ct, TuplesV6Ct,
+                   FwdfIn, FwdfParams, Lb4Out, Lb4Tuples, Rnat4Out, Rnat6Out, Rnf4In, Rnf6In, TuplesV4, TuplesV4Ct, TuplesV6Ct,
                    TuplesV6, check, lib)
 
 CIDR_V4_DYN, CIDR_V4_FIX, CIDR_V6_DYN, CIDR_V6_FIX = 0, 1, 2, 3
@@ -1247,6 +1247,43 @@ class Engine:
                       for k in ("action", "ret", "ifindex", "arg")])
         check(self.L.cgpu_forward_frames(self.h, C.byref(p), C.byref(iv), n, C.byref(ov), _stream(stream)),
               "cgpu_forward_frames")
+        return out
+
+    def rnat_frames(self, f: dict, rn: dict, v6: bool = False, rewrite: bool = True, out: dict | None = None,
+                    stream=None):
+        """cgpu_rnat_frames_v4 / _v6: the reverse NAT a classify_v4_ct /
+        classify_v6_ct(..., rev_nat=True) call decided, written into the
+        frames of the same packets: with `rewrite` the sport, saddr (IPv4
+        loopback: daddr), the IPv4 header checksum and the L4 checksum in
+        f["data"] itself (include/cgpu.h has the rules).  f: the dict of
+        synth.frames_to_device (data, len; flags and ep are not read); rn: any
+        dict holding rn_applied, rn_saddr, rn_sport and for IPv4 rn_daddr (the
+        `out` of those calls goes in as it is).  Returns {"ret"}: 0, or
+        DROP_CSUM_L4 / DROP_SNAPLEN for a frame whose L4 checksum field is out
+        of reach (out={"ret": None}: no ret column)."""
+        import torch
+        need = ("rn_applied", "rn_saddr", "rn_sport") + (() if v6 else ("rn_daddr",))
+        missing = [k for k in need if rn.get(k) is None]
+        if missing:
+            raise ValueError(f"rnat_frames needs the column(s) {missing}")
+        data = f["data"]
+        assert data.dim() == 2 and data.is_contiguous()
+        n = f["len"].numel()
+        if data.shape[0] != n or any(rn[k].numel() != n * (16 if v6 and k == "rn_saddr" else 1) for k in need):
+            raise ValueError("rnat_frames: the frames and the rn columns are not of one batch")
+        if out is None:
+            out = {"ret": torch.empty(n, dtype=torch.int32, device=data.device)}
+        fl = L.RNF_REWRITE if rewrite else 0
+        if v6:
+            iv = Rnf6In(data.data_ptr(), f["len"].data_ptr(), data.shape[1], 0, rn["rn_applied"].data_ptr(),
+                        rn["rn_saddr"].data_ptr(), rn["rn_sport"].data_ptr())
+            check(self.L.cgpu_rnat_frames_v6(self.h, C.byref(iv), fl, n, _ptr(out.get("ret")), _stream(stream)),
+                  "cgpu_rnat_frames_v6")
+        else:
+            iv = Rnf4In(data.data_ptr(), f["len"].data_ptr(), data.shape[1], 0, rn["rn_applied"].data_ptr(),
+                        rn["rn_saddr"].data_ptr(), rn["rn_daddr"].data_ptr(), rn["rn_sport"].data_ptr())
+            check(self.L.cgpu_rnat_frames_v4(self.h, C.byref(iv), fl, n, _ptr(out.get("ret")), _stream(stream)),
+                  "cgpu_rnat_frames_v4")
         return out
 
     def classify_frames_host(self, f: dict, out: dict | None = None, stage: bool = True, stream=None):

@@ -254,6 +254,7 @@ FWD_LXC, FWD_NETDEV = 0, 1
 FWD_ENCAP = 1
 FWDF_REWRITE = 1  # cgpu_forward_frames: rewrite MACs, ttl / hop limit and IPv4 checksum in place
 FLB_REWRITE = 1   # cgpu_classify_frames_lb: store the service step's daddr / saddr / dport and checksums
+RNF_REWRITE = 1   # cgpu_rnat_frames_v4 / _v6: store the reverse NAT's sport / saddr / daddr and checksums
 DROP_WRITE_ERROR, DROP_CSUM_L4 = -141, -154
 FWD_NONE, FWD_DROP, FWD_PROXY, FWD_LOCAL, FWD_HOST, FWD_OVERLAY, FWD_STACK, FWD_TIME_EXCEEDED = range(8)
 DROP_INVALID = -134

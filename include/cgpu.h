@@ -956,8 +956,8 @@ int cgpu_classify_frames_host(cgpu_ctx *ctx, const cgpu_frames *f, size_t n, int
  * CHECKSUM_PARTIAL).  Every new value is computed from the frame as it came
  * and the stores follow in the reference's order; the two differ from the
  * reference only for an IPv4 header with ihl < 5, whose L4 header overlaps
- * the IP header.  Not in scope: the stateful (_ctlb) form on frames, reverse
- * NAT on frames, a _host form, bpf_lb.c's netdev mode, and skb->csum /
+ * the IP header.  Not in scope: the stateful (_ctlb) form on frames (reverse
+ * NAT on frames is cgpu_rnat_frames_v4 / _v6), a _host form, bpf_lb.c's netdev mode, and skb->csum /
  * CHECKSUM_COMPLETE bookkeeping.
  *
  * -EINVAL, judged before the context, for a null struct or a null required
@@ -1274,7 +1274,9 @@ int cgpu_classify_v6_ctlb(cgpu_ctx *ctx, const cgpu_tuples_v6_ct *t, const uint3
  * word; its DROP_UNKNOWN_L4 is unreachable behind ct_lookup's protocol gate);
  * IPv4 with the entry's lb_loopback: daddr := the old saddr; saddr :=
  * nat->address.  Verdicts, ct_ret, identities, counters, metrics and both
- * maps do not depend on this step.  Checksums are not modelled.
+ * maps do not depend on this step.  These calls return the fields as columns;
+ * cgpu_rnat_frames_v4 / _v6, below, write them into raw frames, checksums
+ * included.
  */
 typedef struct cgpu_rnat4_out {
 	uint32_t *saddr, *daddr; /* network order */
@@ -1303,6 +1305,103 @@ int cgpu_classify_v6_ct_rnat(cgpu_ctx *ctx, const cgpu_tuples_v6_ct *t, size_t n
 int cgpu_classify_v6_ctlb_rnat(cgpu_ctx *ctx, const cgpu_tuples_v6_ct *t, const uint32_t *hash, size_t n,
 			       uint32_t now, const cgpu_ctlb6_out *out, const cgpu_rnat6_out *rn,
 			       void *stream);
+
+/*
+ * Reverse NAT on raw frames: what __lb4_rev_nat / __lb6_rev_nat (lib/lb.h:
+ * 485-550, :254-294) write into the packet, with reverse_map_l4_port /
+ * l4_modify_port (lb.h:218-252, lib/l4.h:50-60) and lib/csum.h, for the
+ * decision a cgpu_classify_v{4,6}_ct{,lb}_rnat call has made: a call behind
+ * those, as cgpu_forward_frames is a call behind the classify calls.  The
+ * inputs are the slots of cgpu_frames and the columns the _rnat call wrote
+ * for the same packets; frame i must be the frame whose fields were packet i
+ * of that call.  No table is read (the reverse-NAT map lookup has happened).
+ *
+ * Left alone (every byte kept, ret 0): a frame with applied[i] == 0 (its slot
+ * and its saddr / daddr / sport elements are not read); a frame whose
+ * ethertype is not the call's family; a frame whose fixed header (34 bytes
+ * IPv4, 54 bytes IPv6) does not lie within min(len, stride); and a frame that
+ * cannot have passed ct_lookup: an IPv6 frame whose ipv6_hdrlen walk (the
+ * parse's, cgpu_frames_parse) fails, a protocol other than TCP / UDP / ICMP
+ * (IPv4) or TCP / UDP / ICMPv6 (IPv6), a TCP / UDP frame whose u16 at l4 + 0
+ * does not lie within min(len, stride).
+ *
+ * Offsets: IPv4 l4 = 14 + ihl * 4 and the header's protocol; IPv6 l4 = 14 +
+ * ipv6_hdrlen and nexthdr as that walk leaves it.  The L4 checksum field of
+ * csum_l4_offset_and_flags: TCP l4 + 16, UDP l4 + 6 (BPF_F_MARK_MANGLED_0),
+ * ICMPv6 l4 + 2, IPv4 ICMP none.
+ *
+ * The rewrite of a frame with applied[i] == 1, in the reference's order, with
+ * the arithmetic of cgpu_classify_frames_lb (add, fold, csum_diff, the two
+ * csum_replace forms, the UDP rule) on the words as loaded:
+ *   1. TCP / UDP, sport[i] != the u16 at l4 + 0 (the _rnat call leaves sport
+ *      unchanged when nat->port == 0, so this is the reference's `port &&
+ *      port != old_port`): l4_csum_replace(off, old_port, sport, 2), then the
+ *      port to l4 + 0.
+ *   2. IPv4, daddr[i] != the frame's daddr (ct_state->loopback, whose new
+ *      daddr is the old saddr): daddr to bytes 30..33, D = csum_diff(old_dip,
+ *      new_dip, 0).  Loopback is inferred from the columns: where the
+ *      reference's branch runs with old saddr == old daddr this call starts
+ *      from D = 0 where the reference starts from add(0xFFFFFFFF - x, x) =
+ *      0xFFFFFFFF; every use of D is add(D, ~(u32)c) with ~(u32)c >=
+ *      0xFFFF0000, and add(0xFFFFFFFF, y) == y for y >= 1, so the stored
+ *      checksums are the same.
+ *   3. saddr[i] to bytes 26..29 (IPv6: 22..37), D = csum_diff(old_sip,
+ *      new_sip, D).
+ *   4. IPv4: the header checksum at 24..25 patched by D.
+ *   5. The L4 checksum patched by D with BPF_F_PSEUDO_HDR: IPv4 where the
+ *      protocol has a checksum offset, IPv6 always.
+ *   6. UDP: a checksum field of 0 stays 0 through every patch, a patch that
+ *      yields 0 stores 0xFFFF.
+ *
+ * ret[i] (may be NULL), decided with or without CGPU_RNF_REWRITE: an L4
+ * checksum field the step must patch that lies past len: CGPU_DROP_CSUM_L4;
+ * inside len but past the stored slot: CGPU_DROP_SNAPLEN (an IPv6 TCP frame
+ * needs slots of 80 bytes or more); else 0.  A dropped frame keeps every
+ * byte (the convention of cgpu_classify_frames_lb; without a port change the
+ * reference would already have stored the L3 part before the L4 patch
+ * fails).  Every store lies within len (ct_lookup has loaded the ports), so
+ * CGPU_DROP_WRITE_ERROR is never returned.  The endpoint program returns this
+ * code in place of its verdict (bpf_lxc.c:538-539, :916-917, :783-784): the
+ * call reports it, the caller combines it.
+ *
+ * The frame is taken as carrying full checksums.  Every new value is
+ * computed from the frame as it came and the stores follow in the
+ * reference's order; the two differ from the reference only for an IPv4
+ * header with ihl < 5.  Not in scope: the IPv6 ingress daddr with its index
+ * bits cleared (bpf_lxc.c:753-769), a frame of the _ctlb paths that was both
+ * service-translated and reverse-NATed (the stateful service rewrite does not
+ * exist on frames), a _host form, and skb->csum bookkeeping.
+ *
+ * -EINVAL, judged before the context, for a null struct or a null required
+ * column (data, len, applied, saddr, sport; IPv4: daddr), unknown flag bits,
+ * a nonzero reserved, a misaligned 2- / 4- / 16-byte column (ret included), a
+ * stride that is not a multiple of 16 or is below 64, or data that is not
+ * 16-byte aligned; n == 0 is a no-op that returns 0; -ENODEV on a host-only
+ * context.
+ */
+#define CGPU_RNF_REWRITE 1u
+
+typedef struct cgpu_rnf4_in { /* device pointers */
+	uint8_t *data;                 /* slots as cgpu_frames; written only with CGPU_RNF_REWRITE */
+	const uint32_t *len;
+	uint32_t stride, reserved;     /* stride: multiple of 16, >= 64; reserved 0 */
+	const uint8_t *applied;        /* cgpu_rnat4_out.applied */
+	const uint32_t *saddr, *daddr; /* cgpu_rnat4_out.saddr / .daddr */
+	const uint16_t *sport;         /* cgpu_rnat4_out.sport */
+} cgpu_rnf4_in;
+typedef struct cgpu_rnf6_in { /* device pointers */
+	uint8_t *data;
+	const uint32_t *len;
+	uint32_t stride, reserved;
+	const uint8_t *applied;        /* cgpu_rnat6_out.applied */
+	const uint8_t *saddr;          /* cgpu_rnat6_out.saddr: [n][16], 16-byte aligned */
+	const uint16_t *sport;         /* cgpu_rnat6_out.sport */
+} cgpu_rnf6_in;
+
+int cgpu_rnat_frames_v4(cgpu_ctx *ctx, const cgpu_rnf4_in *in, uint32_t flags, size_t n,
+			int32_t *ret /* may be NULL */, void *stream);
+int cgpu_rnat_frames_v6(cgpu_ctx *ctx, const cgpu_rnf6_in *in, uint32_t flags, size_t n,
+			int32_t *ret /* may be NULL */, void *stream);
 
 /* ------------------------------------------------------------------ */
 /* checkpoint / resume                                      */
