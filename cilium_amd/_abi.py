@@ -140,6 +140,17 @@ class FrameTuples(C.Structure):
                 ("status", "family", "saddr", "daddr", "dport", "proto", "flags")]
 
 
+class FrameCtCols(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in
+                ("status", "family", "saddr", "daddr", "sport", "dport", "proto", "l4", "flags")]
+
+
+class FctOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in
+                ("status", "family", "verdict", "ct_ret", "identity", "stage",
+                 "rn_applied", "rn_sport", "rn_saddr4", "rn_daddr4", "rn_saddr6")]
+
+
 vp, sz, u32, u64, i32 = C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint64, C.c_int
 u16 = C.c_uint16
 
@@ -278,6 +289,8 @@ PROTOS = {
                                          C.POINTER(Rnat6Out), vp]),
     "cgpu_rnat_frames_v4": (i32, [vp, C.POINTER(Rnf4In), u32, sz, vp, vp]),
     "cgpu_rnat_frames_v6": (i32, [vp, C.POINTER(Rnf6In), u32, sz, vp, vp]),
+    "cgpu_frames_parse_ct": (i32, [vp, C.POINTER(Frames), sz, C.POINTER(FrameCtCols), vp]),
+    "cgpu_classify_frames_ct": (i32, [vp, C.POINTER(Frames), sz, u32, C.POINTER(FctOut), vp]),
     "cgpu_l3_compile":(i32, [vp, vp, vp, vp, u32, vp]),
     "cgpu_mapstate_sync": (i32, [vp, vp, vp, vp, vp, vp]),
     "cgpu_counter_delta_bytes": (sz, [vp]),

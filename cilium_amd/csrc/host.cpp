@@ -2094,6 +2094,15 @@ struct cgpu_ctx {
 	size_t ct_scratch_cap = 0;
 	hipStream_t ct_stream = nullptr; /* the conntrack path's internal stream */
 	hipEvent_t ct_done = nullptr;
+	/* cgpu_classify_frames_ct: its calls serialise on fct_mu (taken before mu,
+	 * never the other way round); the scratch (grow-only), the two packet
+	 * counts the host reads, and the event behind the last call's scatter,
+	 * which the next call's stream waits for before it writes the scratch */
+	std::mutex fct_mu;
+	void *d_fct = nullptr;
+	size_t fct_cap = 0;
+	uint32_t *d_fct_n = nullptr;
+	hipEvent_t fct_done = nullptr;
 };
 
 namespace {
@@ -2393,6 +2402,10 @@ CGPU_EXPORT void cgpu_ctx_destroy(cgpu_ctx *c)
 		}
 		(void)hipFree(c->d_ct_scratch);
 		(void)hipFree(c->d_ct_pk);
+		(void)hipFree(c->d_fct);
+		(void)hipFree(c->d_fct_n);
+		if (c->fct_done)
+			(void)hipEventDestroy(c->fct_done);
 		(void)hipFree(c->d_rn4);
 		(void)hipFree(c->d_rn6);
 		host_stage_free(c);
@@ -7593,6 +7606,236 @@ CGPU_EXPORT int cgpu_classify_v6_ctlb_rnat(cgpu_ctx *c, const cgpu_tuples_v6_ct 
 	CtOuts o;
 	CtRnat r;
 	return classify_ct(c, t, hash, n, now, true, ct_outs(out, o), nullptr, ct_rnat(rn, r), stream);
+}
+
+/* ======================================================================= */
+/* raw frames to the stateful path (cgpu.h cgpu_frames_parse_ct,             */
+/* cgpu_classify_frames_ct)                                                  */
+/* ======================================================================= */
+static_assert(sizeof(cgpu_frame_ct_cols) == 72 && offsetof(cgpu_frame_ct_cols, l4) == 56,
+	      "cgpu_frame_ct_cols layout");
+static_assert(sizeof(cgpu_fct_out) == 88 && offsetof(cgpu_fct_out, rn_applied) == 48, "cgpu_fct_out layout");
+
+/* the frames argument of both calls, judged before the context */
+static int frames_ct_check(const cgpu_frames *f, size_t n)
+{
+	if (f->stride < 64 || (f->stride & 15))
+		return fail(-EINVAL, "frame stride must be a multiple of 16 and >= 64");
+	if ((uintptr_t)f->data & 15)
+		return fail(-EINVAL, "frame buffer must be 16-byte aligned");
+	if (f->reserved)
+		return fail(-EINVAL, "nonzero reserved");
+	if (n && (!f->data || !f->len || !f->flags || !f->ep))
+		return fail(-EINVAL, "null frame column");
+	if ((uintptr_t)f->len & 3u)
+		return fail(-EINVAL, "4-byte column not 4-byte aligned");
+	if ((uintptr_t)f->ep & 1u)
+		return fail(-EINVAL, "2-byte column not 2-byte aligned");
+	return 0;
+}
+
+/* and the context's part: a device, and the CONNTRACK build's protocol gate */
+static int frames_ct_ctx(const cgpu_ctx *c)
+{
+	if (c->device < 0)
+		return fail(-ENODEV, "context has no device (host-only); no CPU path");
+	if (!c->cfg.ct_proto_gate)
+		return fail(-EINVAL, "the stateful path needs ct_proto_gate (CONNTRACK): without it the parse "
+				     "bounds no L4 load");
+	return 0;
+}
+
+CGPU_EXPORT int cgpu_frames_parse_ct(cgpu_ctx *c, const cgpu_frames *f, size_t n,
+				     const cgpu_frame_ct_cols *o, void *stream)
+{
+	if (!c || !f || !o)
+		return fail(-EINVAL, "null argument");
+	if (int r = frames_ct_check(f, n))
+		return r;
+	if (n && !o->status)
+		return fail(-EINVAL, "null status output");
+	if ((uintptr_t)o->status & 3u)
+		return fail(-EINVAL, "4-byte column not 4-byte aligned");
+	if (((uintptr_t)o->sport | (uintptr_t)o->dport | (uintptr_t)o->l4) & 1u)
+		return fail(-EINVAL, "2-byte column not 2-byte aligned");
+	if (((uintptr_t)o->saddr | (uintptr_t)o->daddr) & 15u)
+		return fail(-EINVAL, "address rows not 16-byte aligned");
+	if (int r = frames_ct_ctx(c))
+		return r;
+	if (!n)
+		return 0;
+	Pinned P;
+	if (int r = pin(c, stream, P))
+		return r;
+	const frames_ct_args a{f->data, f->len, f->flags, f->ep, f->stride, (uint64_t)n,
+			       o->status, o->family, o->saddr, o->daddr, o->sport, o->dport,
+			       o->proto, o->l4, o->flags};
+	HIP_OR_EIO(launch_frames_ct_parse(P.snap(), a, nullptr, (hipStream_t)stream));
+	return 0;
+}
+
+CGPU_EXPORT int cgpu_classify_frames_ct(cgpu_ctx *c, const cgpu_frames *f, size_t n, uint32_t now,
+					const cgpu_fct_out *o, void *stream)
+{
+	if (!c || !f || !o)
+		return fail(-EINVAL, "null argument");
+	if (int r = frames_ct_check(f, n))
+		return r;
+	if (n && (!o->verdict || !o->ct_ret || !o->identity))
+		return fail(-EINVAL, "null verdict, ct_ret or identity output");
+	const int n_rn = !!o->rn_applied + !!o->rn_sport + !!o->rn_saddr4 + !!o->rn_daddr4 + !!o->rn_saddr6;
+	if (n_rn != 0 && n_rn != 5)
+		return fail(-EINVAL, "the reverse NAT outputs are given all five or not at all");
+	if (((uintptr_t)o->status | (uintptr_t)o->verdict | (uintptr_t)o->identity | (uintptr_t)o->rn_saddr4 |
+	     (uintptr_t)o->rn_daddr4) & 3u)
+		return fail(-EINVAL, "4-byte column not 4-byte aligned");
+	if ((uintptr_t)o->rn_sport & 1u)
+		return fail(-EINVAL, "2-byte column not 2-byte aligned");
+	if ((uintptr_t)o->rn_saddr6 & 15u)
+		return fail(-EINVAL, "address rows not 16-byte aligned");
+	if (n > (size_t)INT32_MAX)
+		return fail(-EINVAL, "batch of %zu frames exceeds 2^31 - 1", n);
+	if (int r = frames_ct_ctx(c))
+		return r;
+	if (!n)
+		return 0;
+	const bool rn = n_rn == 5;
+	const hipStream_t st = (hipStream_t)stream;
+	std::lock_guard<std::mutex> g(c->fct_mu);
+	Pinned P;
+	if (int r = pin(c, stream, P))
+		return r;
+	/* the scratch: the parsed columns (42 B per frame), the two index lists
+	 * (8), the selections' block counts, then the compacted packets and their
+	 * results (IPv4 43 B, IPv6 75 B per packet, carved once the counts are
+	 * known: at most 75 n) */
+	size_t total = 0;
+	auto take = [&](size_t bytes) {
+		const size_t off = total;
+		total += (bytes + 255) & ~(size_t)255;
+		return off;
+	};
+	const size_t o_sa = take(n * 16), o_da = take(n * 16), o_sp = take(n * 2), o_dp = take(n * 2),
+		     o_l4 = take(n * 2), o_pr = take(n), o_fl = take(n), o_s4 = take(n), o_s6 = take(n),
+		     o_i4 = take(n * 4), o_i6 = take(n * 4), o_tmp = take(fct_select_bytes(n));
+	const size_t o_cmp = total;
+	total += n * 75 + 34 * 256;
+	if (!c->d_fct_n) {
+		HIP_OR_EIO(hipMalloc((void **)&c->d_fct_n, 8));
+		if (hipEventCreateWithFlags(&c->fct_done, hipEventDisableTiming) != hipSuccess) {
+			(void)hipFree(c->d_fct_n);
+			c->d_fct_n = nullptr;
+			c->fct_done = nullptr;
+			return fail(-EIO, "event create failed");
+		}
+	}
+	if (total > c->fct_cap) {
+		HIP_OR_EIO(hipEventSynchronize(c->fct_done));
+		(void)hipFree(c->d_fct);
+		c->d_fct = nullptr;
+		c->fct_cap = 0;
+		HIP_OR_EIO(hipMalloc(&c->d_fct, total));
+		c->fct_cap = total;
+	}
+	/* the previous call's last pass (maybe on another stream) is done with the scratch */
+	HIP_OR_EIO(hipStreamWaitEvent(st, c->fct_done, 0));
+	struct Done { /* whatever this call enqueued on st ends before the next call's first write */
+		cgpu_ctx *c;
+		hipStream_t st;
+		~Done() { (void)hipEventRecord(c->fct_done, st); }
+	} done{c, st};
+	uint8_t *b = static_cast<uint8_t *>(c->d_fct);
+	const cgpu_snapshot &s = P.snap();
+	const frames_ct_args pa{f->data, f->len, f->flags, f->ep, f->stride, (uint64_t)n,
+				o->status, o->family, b + o_sa, b + o_da,
+				reinterpret_cast<uint16_t *>(b + o_sp), reinterpret_cast<uint16_t *>(b + o_dp),
+				b + o_pr, reinterpret_cast<uint16_t *>(b + o_l4), b + o_fl};
+	const fct_outs fo{o->verdict, o->ct_ret, o->identity, o->stage, o->rn_applied, o->rn_sport,
+			  o->rn_saddr4, o->rn_daddr4, o->rn_saddr6};
+	const fct_fin fin{fo, b + o_s4, b + o_s6, P.delta};
+	HIP_OR_EIO(launch_frames_ct_parse(s, pa, &fin, st));
+	uint32_t *idx[2] = {reinterpret_cast<uint32_t *>(b + o_i4), reinterpret_cast<uint32_t *>(b + o_i6)};
+	HIP_OR_EIO(launch_fct_select(fin.sel4, n, idx[0], c->d_fct_n, b + o_tmp, st));
+	HIP_OR_EIO(launch_fct_select(fin.sel6, n, idx[1], c->d_fct_n + 1, b + o_tmp, st));
+	uint32_t cnt[2] = {0, 0};
+	HIP_OR_EIO(hipMemcpyAsync(cnt, c->d_fct_n, 8, hipMemcpyDeviceToHost, st));
+	HIP_OR_EIO(hipStreamSynchronize(st));
+	if ((uint64_t)cnt[0] + cnt[1] > n)
+		return fail(-EIO, "frame selection counted %u + %u of %zu frames", cnt[0], cnt[1], n);
+	size_t cur = o_cmp;
+	auto carve = [&](size_t bytes) {
+		uint8_t *p = b + cur;
+		cur += (bytes + 255) & ~(size_t)255;
+		return p;
+	};
+	fct_compact C[2];
+	for (int v6 = 0; v6 < 2; v6++) {
+		fct_compact &k = C[v6];
+		const size_t m = cnt[v6], ab = v6 ? 16 : 4;
+		k = fct_compact{};
+		k.idx = idx[v6];
+		k.m = m;
+		k.v6 = v6;
+		if (!m)
+			continue;
+		k.saddr = carve(m * ab);
+		k.daddr = carve(m * ab);
+		k.sport = reinterpret_cast<uint16_t *>(carve(m * 2));
+		k.dport = reinterpret_cast<uint16_t *>(carve(m * 2));
+		k.proto = carve(m);
+		k.l4 = reinterpret_cast<uint16_t *>(carve(m * 2));
+		k.flags = carve(m);
+		k.len = reinterpret_cast<uint32_t *>(carve(m * 4));
+		k.ep = reinterpret_cast<uint16_t *>(carve(m * 2));
+		k.verdict = reinterpret_cast<int32_t *>(carve(m * 4));
+		k.ct_ret = carve(m);
+		k.identity = reinterpret_cast<uint32_t *>(carve(m * 4));
+		if (o->stage)
+			k.stage = carve(m);
+		if (rn) {
+			k.rn_applied = carve(m);
+			k.rn_sport = reinterpret_cast<uint16_t *>(carve(m * 2));
+			k.rn_saddr = carve(m * ab);
+			if (!v6)
+				k.rn_daddr = reinterpret_cast<uint32_t *>(carve(m * 4));
+		}
+	}
+	if (cur > total)
+		return fail(-EIO, "frames conntrack scratch carved past its end");
+	for (int v6 = 0; v6 < 2; v6++) {
+		const fct_compact &k = C[v6];
+		if (!k.m)
+			continue;
+		HIP_OR_EIO(launch_fct_gather(pa, k, st));
+		ct_launch a{};
+		a.saddr = k.saddr;
+		a.daddr = k.daddr;
+		a.sport = k.sport;
+		a.dport = k.dport;
+		a.proto = k.proto;
+		a.l4 = k.l4;
+		a.flags = k.flags;
+		a.len = k.len;
+		a.ep = k.ep;
+		a.verdict = k.verdict;
+		a.ct_ret = k.ct_ret;
+		a.identity = k.identity;
+		a.stage = k.stage;
+		a.n = k.m;
+		a.now = now;
+		a.tun = &P.tun();
+		if (rn) {
+			a.rn_saddr = k.rn_saddr;
+			a.rn_daddr = k.rn_daddr;
+			a.rn_sport = k.rn_sport;
+			a.rn_applied = k.rn_applied;
+		}
+		/* the conntrack call of the family, on the snapshot pinned above */
+		if (int r = ct_classify(c, s, P.delta, v6 ? c->ct6 : c->ct4, a, stream, false, rn))
+			return r;
+		HIP_OR_EIO(launch_fct_scatter(k, fo, rn, st));
+	}
+	return 0;
 }
 
 /* ======================================================================= */

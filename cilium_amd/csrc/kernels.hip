@@ -10351,3 +10351,239 @@ hipError_t launch_l3_compile(const l3_launch &L, hipStream_t st)
 				   dim3(256), 0, st, P);
 	return hipGetLastError();
 }
+
+/* ------------------------------------------------------------------ */
+/* raw frames -> the stateful path (cgpu_frames_parse_ct,               */
+/* cgpu_classify_frames_ct)                                             */
+/* ------------------------------------------------------------------ */
+/* k_frames<0>'s shape (one frame per lane, the slot's first 64 bytes by four
+ * ld_x4, parse_frame_w) with the columns ct_lookup4 / ct_lookup6 read beside
+ * the policy tuple: the wire ports at l4 + 0 / + 2 and the TCP flag word at
+ * l4 + 12 or the ICMP type at l4, as loaded.  parse_frame_w has bounded every
+ * one of those loads for a frame it returns with status 0 (ct_proto_gate is
+ * on: the host refuses the call otherwise), so they are read without another
+ * check: from the window for an option-less IPv4 header (l4 = 34: ports at
+ * 34 / 36, flag word at 46) and the ports of an extension-less IPv6 header
+ * (54 / 56), by global loads inside min(len, stride) otherwise -- one for the
+ * flag word of that IPv6 frame (bytes 66-67), up to three behind IPv4 options
+ * or IPv6 extension headers (whose walk is redone to find l4: rare).
+ * FIN (cgpu_classify_frames_ct's parse pass): a frame that ends here gets its
+ * final outputs and its metrics by k_frames<1>'s rule; a frame that goes on
+ * gets the rn address columns of the other family zeroed; one select byte per
+ * family feeds the compaction. */
+template <bool FIN>
+__global__ __launch_bounds__(BLOCK) void k_frames_ct(cgpu_snapshot s, frames_ct_args a, fct_fin F)
+{
+	uint64_t *met = FIN ? F.delta + 2ull * s.n_ctr_slots : nullptr;
+	uint64_t gcnt[2] = {0, 0}, gbyt[2] = {0, 0}; /* -137 frames {ingress, egress} */
+	const uint64_t gstride = (uint64_t)gridDim.x * BLOCK;
+	for (uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i < a.n; i += gstride) {
+		const uint32_t len = a.len[i];
+		const bool egress = a.flags[i] & 1u;
+		const uint32_t ep = a.ep[i];
+		const uint8_t *f = a.data + i * (uint64_t)a.stride;
+		const uint32_t cap = min(len, a.stride);
+		fwin W;
+#pragma unroll
+		for (int k = 0; k < 4; k++) {
+			const uint4 v = ld_x4<true>(f + 16 * k);
+			W.w[4 * k] = v.x;
+			W.w[4 * k + 1] = v.y;
+			W.w[4 * k + 2] = v.z;
+			W.w[4 * k + 3] = v.w;
+		}
+		const ftuple t = parse_frame_w(s, W, f, len, cap, egress, ep, s.lxc);
+		uint32_t sport = 0, dport = 0, l4w = 0;
+		if (t.status == 0) {
+			const bool v4 = t.fam == 4u;
+			uint32_t l4 = v4 ? 14u + 4u * (W.b(14) & 15u) : 54u;
+			/* IPv6: the walk left nexthdr as it was iff there was no extension header */
+			const bool inwin = v4 ? l4 == 34u : W.b(20) == t.proto;
+			if (!v4 && !inwin) {
+				uint32_t nh = W.b(20), off;
+				(void)ipv6_walk(f, len, cap, nh, off);
+				l4 = 14u + off;
+			}
+			if (t.proto == 6u || t.proto == 17u) {
+				sport = inwin ? (v4 ? W.h(34) : W.h(54)) : ld_h(f + l4);
+				dport = inwin ? (v4 ? W.h(36) : W.h(56)) : ld_h(f + l4 + 2u);
+				if (t.proto == 6u)
+					l4w = (inwin && v4) ? W.h(46) : ld_h(f + l4 + 12u);
+			} else {
+				l4w = inwin ? (v4 ? W.b(34) : W.b(54)) : (uint32_t)f[l4];
+			}
+		}
+		const uint32_t tfl = (egress ? 1u : 0u) | (t.frag ? 2u : 0u);
+		if (a.status)
+			a.status[i] = t.status;
+		if (a.family)
+			a.family[i] = (uint8_t)t.fam;
+		if (a.saddr16)
+			reinterpret_cast<uint4 *>(a.saddr16)[i] = t.sa;
+		if (a.daddr16)
+			reinterpret_cast<uint4 *>(a.daddr16)[i] = t.da;
+		if (a.sport)
+			a.sport[i] = (uint16_t)sport;
+		if (a.dport)
+			a.dport[i] = (uint16_t)dport;
+		if (a.proto)
+			a.proto[i] = (uint8_t)t.proto;
+		if (a.l4)
+			a.l4[i] = (uint16_t)l4w;
+		if (a.tflags)
+			a.tflags[i] = (uint8_t)tfl;
+		if (!FIN)
+			continue;
+		const bool go = t.status == 0;
+		F.sel4[i] = go && t.fam == 4u ? 1u : 0u;
+		F.sel6[i] = go && t.fam == 6u ? 1u : 0u;
+		const bool rn = F.o.rn_applied != nullptr;
+		if (go) {
+			if (rn) {
+				if (t.fam == 4u) {
+					reinterpret_cast<uint4 *>(F.o.rn_saddr6)[i] = uint4{0, 0, 0, 0};
+				} else {
+					F.o.rn_saddr4[i] = 0u;
+					F.o.rn_daddr4[i] = 0u;
+				}
+			}
+			continue;
+		}
+		const bool nc = t.status == FRAME_NOT_CLASSIFIED;
+		const int32_t v = nc ? 0 : t.status;
+		F.o.verdict[i] = v;
+		F.o.ct_ret[i] = (uint8_t)CGPU_CT_NONE;
+		F.o.identity[i] = 0u;
+		if (F.o.stage)
+			F.o.stage[i] = (uint8_t)(nc ? CGPU_STAGE_NOT_CLASSIFIED : v == DROP_CT_UNKNOWN_PROTO ? 4u : 5u);
+		if (rn) {
+			F.o.rn_applied[i] = 0u;
+			F.o.rn_sport[i] = 0u;
+			F.o.rn_saddr4[i] = 0u;
+			F.o.rn_daddr4[i] = 0u;
+			reinterpret_cast<uint4 *>(F.o.rn_saddr6)[i] = uint4{0, 0, 0, 0};
+		}
+		/* update_metrics(len, dir, -reason) as k_frames<1>: not classified and
+		 * snap-length frames count nothing.  The untracked protocols (-137, a
+		 * per cent of a conntrack stream, all on two words) are summed per
+		 * lane and per wave; the other reasons go out directly */
+		if (nc || v == DROP_SNAPLEN)
+			continue;
+		if (v == DROP_CT_UNKNOWN_PROTO) {
+			gcnt[egress ? 1 : 0] += 1u;
+			gbyt[egress ? 1 : 0] += len;
+			continue;
+		}
+		const uint32_t key = (((uint32_t)(-v) & 0xffu) * 4u + (egress ? 1u : 0u) + 1u) * 2u;
+		atomicAdd((unsigned long long *)&met[key], 1ull);
+		atomicAdd((unsigned long long *)&met[key + 1], (unsigned long long)len);
+	}
+	if (!FIN)
+		return;
+#pragma unroll
+	for (int k = 0; k < 2; k++) {
+		const uint64_t c = wave_sum(gcnt[k]);
+		const uint64_t b = wave_sum(gbyt[k]);
+		if ((threadIdx.x & 63) == 0 && c) {
+			const uint32_t key = (137u * 4u + (uint32_t)k + 1u) * 2u;
+			atomicAdd((unsigned long long *)&met[key], (unsigned long long)c);
+			atomicAdd((unsigned long long *)&met[key + 1], (unsigned long long)b);
+		}
+	}
+}
+
+hipError_t launch_frames_ct_parse(const cgpu_snapshot &s, const frames_ct_args &a, const fct_fin *fin,
+				  hipStream_t st)
+{
+	if (fin)
+		hipLaunchKernelGGL(k_frames_ct<true>, dim3(grid_for(a.n)), dim3(BLOCK), 0, st, s, a, *fin);
+	else
+		hipLaunchKernelGGL(k_frames_ct<false>, dim3(grid_for(a.n)), dim3(BLOCK), 0, st, s, a, fct_fin{});
+	return hipGetLastError();
+}
+
+size_t fct_select_bytes(uint64_t n)
+{
+	return (size_t)(sel_blocks(n) + 1u) * 4u;
+}
+
+hipError_t launch_fct_select(const uint8_t *sel, uint64_t n, uint32_t *idx, uint32_t *count, void *temp,
+			     hipStream_t st)
+{
+	return ct_select(sel, n, idx, count, static_cast<uint32_t *>(temp), st);
+}
+
+/* the conntrack call's input columns of one family, compacted: packet j is
+ * frame idx[j] (ascending, so each family keeps the batch's order) */
+template <bool V6> __global__ __launch_bounds__(BLOCK) void k_fct_gather(frames_ct_args a, fct_compact c)
+{
+	const uint64_t gstride = (uint64_t)gridDim.x * BLOCK;
+	for (uint64_t j = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; j < c.m; j += gstride) {
+		const uint64_t i = c.idx[j];
+		if (V6) {
+			static_cast<uint4 *>(c.saddr)[j] = reinterpret_cast<const uint4 *>(a.saddr16)[i];
+			static_cast<uint4 *>(c.daddr)[j] = reinterpret_cast<const uint4 *>(a.daddr16)[i];
+		} else {
+			static_cast<uint32_t *>(c.saddr)[j] = reinterpret_cast<const uint4 *>(a.saddr16)[i].x;
+			static_cast<uint32_t *>(c.daddr)[j] = reinterpret_cast<const uint4 *>(a.daddr16)[i].x;
+		}
+		c.sport[j] = a.sport[i];
+		c.dport[j] = a.dport[i];
+		c.proto[j] = a.proto[i];
+		c.l4[j] = a.l4[i];
+		c.flags[j] = a.tflags[i];
+		c.len[j] = a.len[i];
+		c.ep[j] = a.ep[i];
+	}
+}
+
+hipError_t launch_fct_gather(const frames_ct_args &src, const fct_compact &c, hipStream_t st)
+{
+	if (!c.m)
+		return hipSuccess;
+	if (c.v6)
+		hipLaunchKernelGGL(k_fct_gather<true>, dim3(grid_for(c.m)), dim3(BLOCK), 0, st, src, c);
+	else
+		hipLaunchKernelGGL(k_fct_gather<false>, dim3(grid_for(c.m)), dim3(BLOCK), 0, st, src, c);
+	return hipGetLastError();
+}
+
+/* the conntrack call's outputs back to frame order: out[idx[j]] = compact[j] */
+template <bool V6, bool RN> __global__ __launch_bounds__(BLOCK) void k_fct_scatter(fct_compact c, fct_outs o)
+{
+	const uint64_t gstride = (uint64_t)gridDim.x * BLOCK;
+	for (uint64_t j = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; j < c.m; j += gstride) {
+		const uint64_t i = c.idx[j];
+		o.verdict[i] = c.verdict[j];
+		o.ct_ret[i] = c.ct_ret[j];
+		o.identity[i] = c.identity[j];
+		if (o.stage)
+			o.stage[i] = c.stage[j];
+		if (RN) {
+			o.rn_applied[i] = c.rn_applied[j];
+			o.rn_sport[i] = c.rn_sport[j];
+			if (V6) {
+				reinterpret_cast<uint4 *>(o.rn_saddr6)[i] = static_cast<const uint4 *>(c.rn_saddr)[j];
+			} else {
+				o.rn_saddr4[i] = static_cast<const uint32_t *>(c.rn_saddr)[j];
+				o.rn_daddr4[i] = c.rn_daddr[j];
+			}
+		}
+	}
+}
+
+hipError_t launch_fct_scatter(const fct_compact &c, const fct_outs &o, bool rn, hipStream_t st)
+{
+	if (!c.m)
+		return hipSuccess;
+	const dim3 g(grid_for(c.m)), b(BLOCK);
+	if (c.v6 && rn)
+		hipLaunchKernelGGL((k_fct_scatter<true, true>), g, b, 0, st, c, o);
+	else if (c.v6)
+		hipLaunchKernelGGL((k_fct_scatter<true, false>), g, b, 0, st, c, o);
+	else if (rn)
+		hipLaunchKernelGGL((k_fct_scatter<false, true>), g, b, 0, st, c, o);
+	else
+		hipLaunchKernelGGL((k_fct_scatter<false, false>), g, b, 0, st, c, o);
+	return hipGetLastError();
+}

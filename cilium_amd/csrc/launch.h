@@ -265,6 +265,77 @@ struct rnat_frames_args {
 };
 hipError_t launch_rnat_frames(const rnat_frames_args &a, hipStream_t st);
 
+/* frames to the stateful path (cgpu_frames_parse_ct / cgpu_classify_frames_ct):
+ * the slots of cgpu_frames and the columns of cgpu_frame_ct_cols (any but
+ * status may be NULL).  launch_frames_ct_parse with fin != NULL is the parse
+ * pass of cgpu_classify_frames_ct: it also writes the final outputs of the
+ * frames that end in the parse (and the other family's rn columns of the
+ * rest), counts their metrics and writes one select byte per family. */
+struct frames_ct_args {
+	const uint8_t *data;
+	const uint32_t *len;
+	const uint8_t *flags;
+	const uint16_t *ep;
+	uint32_t stride;
+	uint64_t n;
+	int32_t *status;
+	uint8_t *family, *saddr16, *daddr16;
+	uint16_t *sport, *dport;
+	uint8_t *proto;
+	uint16_t *l4;
+	uint8_t *tflags;
+};
+/* the frame-order outputs of cgpu_fct_out (stage and the rn group may be NULL) */
+struct fct_outs {
+	int32_t *verdict;
+	uint8_t *ct_ret;
+	uint32_t *identity;
+	uint8_t *stage;
+	uint8_t *rn_applied;
+	uint16_t *rn_sport;
+	uint32_t *rn_saddr4, *rn_daddr4;
+	uint8_t *rn_saddr6;
+};
+struct fct_fin {
+	fct_outs o;
+	uint8_t *sel4, *sel6; /* [n] 1: the frame reaches conntrack in that family */
+	uint64_t *delta;
+};
+hipError_t launch_frames_ct_parse(const cgpu_snapshot &s, const frames_ct_args &a, const fct_fin *fin,
+				  hipStream_t st);
+/* bytes of block-count scratch launch_fct_select wants for n frames */
+size_t fct_select_bytes(uint64_t n);
+/* idx[0, *count) = the ascending i < n with sel[i] != 0 */
+hipError_t launch_fct_select(const uint8_t *sel, uint64_t n, uint32_t *idx, uint32_t *count, void *temp,
+			     hipStream_t st);
+/* one family's compact columns: m packets, the conntrack call's inputs and
+ * outputs (saddr / daddr / rn_saddr: u32 per packet, or 16-byte rows) */
+struct fct_compact {
+	const uint32_t *idx;
+	uint64_t m;
+	void *saddr, *daddr;
+	uint16_t *sport, *dport;
+	uint8_t *proto;
+	uint16_t *l4;
+	uint8_t *flags;
+	uint32_t *len;
+	uint16_t *ep;
+	int32_t *verdict;
+	uint8_t *ct_ret;
+	uint32_t *identity;
+	uint8_t *stage;
+	uint8_t *rn_applied;
+	uint16_t *rn_sport;
+	void *rn_saddr;
+	uint32_t *rn_daddr;
+	int v6;
+};
+/* compact[j] = column[idx[j]] for the inputs (src: the parse's columns; len
+ * and ep from the frames' own) */
+hipError_t launch_fct_gather(const frames_ct_args &src, const fct_compact &c, hipStream_t st);
+/* out[idx[j]] = compact[j] for the outputs (rn: with the rn group) */
+hipError_t launch_fct_scatter(const fct_compact &c, const fct_outs &o, bool rn, hipStream_t st);
+
 /* stateful classification (cgpu_classify_v4_ct): packet columns, outputs,
  * and the caller-allocated scratch (ct_scratch_layout in host.cpp) */
 struct ct_launch {

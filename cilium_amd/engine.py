@@ -25,7 +25,7 @@ import ipaddress
 import numpy as np
 
 from . import layouts as L
-from ._abi import (CgpuConfig, CgpuError, CtlbOut, DlvIn, DlvOut, FlbIn, FlbOut, FrameTuples, Frames, FwdIn, FwdOut,
+from ._abi import (CgpuConfig, CgpuError, CtlbOut, DlvIn, DlvOut, FctOut, FlbIn, FlbOut, FrameCtCols, FrameTuples, Frames, FwdIn, FwdOut,
                    FwdParams,
                    FwdfIn, FwdfParams, Lb4Out, Lb4Tuples, Rnat4Out, Rnat6Out, Rnf4In, Rnf6In, TuplesV4, TuplesV4Ct, TuplesV6Ct,
                    TuplesV6, check, lib)
@@ -1138,6 +1138,85 @@ class Engine:
                                                       "dport", "proto", "flags")])
         check(self.L.cgpu_frames_parse(self.h, C.byref(fr), n, C.byref(ot), _stream(stream)),
               "cgpu_frames_parse")
+        return out
+
+    def frames_parse_ct(self, f: dict, out: dict | None = None, stream=None):
+        """cgpu_frames_parse_ct: the frames' columns for the stateful path.
+        f as frames_parse.  Returns status, family, saddr / daddr ((n, 16)
+        uint8), sport / dport (int16: the wire ports as loaded), proto, l4b
+        (int16: TCP header bytes 12-13 / the ICMP type, the conntrack dicts'
+        name for cgpu_tuples_v4_ct.l4) and flags; a frame with status != 0 has
+        sport, dport and l4b of 0.  In a given `out` every key but status may
+        be None or missing (that column is not written)."""
+        import torch
+        n = f["len"].numel()
+        dev = f["len"].device
+        if out is None:
+            out = {"status": torch.empty(n, dtype=torch.int32, device=dev),
+                   "family": torch.empty(n, dtype=torch.uint8, device=dev),
+                   "saddr": torch.empty((n, 16), dtype=torch.uint8, device=dev),
+                   "daddr": torch.empty((n, 16), dtype=torch.uint8, device=dev),
+                   "sport": torch.empty(n, dtype=torch.int16, device=dev),
+                   "dport": torch.empty(n, dtype=torch.int16, device=dev),
+                   "proto": torch.empty(n, dtype=torch.uint8, device=dev),
+                   "l4b": torch.empty(n, dtype=torch.int16, device=dev),
+                   "flags": torch.empty(n, dtype=torch.uint8, device=dev)}
+        fr = self._frames(f)
+        ot = FrameCtCols(*[_ptr(out.get(k)) for k in ("status", "family", "saddr", "daddr", "sport", "dport",
+                                                      "proto", "l4b", "flags")])
+        check(self.L.cgpu_frames_parse_ct(self.h, C.byref(fr), n, C.byref(ot), _stream(stream)),
+              "cgpu_frames_parse_ct")
+        return out
+
+    def classify_frames_ct(self, f: dict, now: int, out: dict | None = None, stage: bool = True,
+                           rev_nat: dict | None = None, stream=None):
+        """cgpu_classify_frames_ct: the stateful decision on a mixed batch of
+        raw frames, in frame order (include/cgpu.h has the rules).  Returns
+        status, family, verdict, ct_ret, identity, stage.  The call waits on
+        the host and cannot be captured into a graph.
+        rev_nat=dict(rewrite=True | False): the _rnat conntrack calls run, and
+        out gains rn_applied, rn_sport, rn_saddr / rn_daddr (int32, the IPv4
+        frames') and rn_saddr6 ((n, 16) uint8, the IPv6 frames'); then
+        rnat_frames runs once per family on the same frames (with rewrite, the
+        default, f["data"] is modified in place; each call leaves the other
+        family's frames alone) and out["rn_ret"] holds each frame's ret of its
+        family's call, 0 for a frame that is not IP."""
+        import torch
+        n = f["len"].numel()
+        dev = f["len"].device
+        if rev_nat is not None:
+            bad = set(rev_nat) - {"rewrite"}
+            if bad:
+                raise TypeError(f"unknown rev_nat parameter(s) {sorted(bad)}")
+        if out is None:
+            out = {}
+        for k, dt in (("status", torch.int32), ("family", torch.uint8), ("verdict", torch.int32),
+                      ("ct_ret", torch.uint8), ("identity", torch.int32), ("stage", torch.uint8)):
+            if k not in out:
+                out[k] = torch.empty(n, dtype=dt, device=dev) if (stage or k != "stage") else None
+        if rev_nat is not None:
+            for k, dt in (("rn_applied", torch.uint8), ("rn_sport", torch.int16), ("rn_saddr", torch.int32),
+                          ("rn_daddr", torch.int32)):
+                if out.get(k) is None:
+                    out[k] = torch.empty(n, dtype=dt, device=dev)
+            if out.get("rn_saddr6") is None:
+                out["rn_saddr6"] = torch.empty((n, 16), dtype=torch.uint8, device=dev)
+            if out.get("family") is None:  # rn_ret is picked by it
+                out["family"] = torch.empty(n, dtype=torch.uint8, device=dev)
+        rnk = ("rn_applied", "rn_sport", "rn_saddr", "rn_daddr", "rn_saddr6")
+        fr = self._frames(f)
+        ov = FctOut(*[_ptr(out.get(k)) for k in ("status", "family", "verdict", "ct_ret", "identity", "stage")],
+                    *[_ptr(out.get(k)) if rev_nat is not None else None for k in rnk])
+        check(self.L.cgpu_classify_frames_ct(self.h, C.byref(fr), n, now, C.byref(ov), _stream(stream)),
+              "cgpu_classify_frames_ct")
+        if rev_nat is not None:
+            rw = bool(rev_nat.get("rewrite", True))
+            r4 = self.rnat_frames(f, out, v6=False, rewrite=rw, stream=stream)["ret"]
+            r6 = self.rnat_frames(f, {"rn_applied": out["rn_applied"], "rn_sport": out["rn_sport"],
+                                      "rn_saddr": out["rn_saddr6"]}, v6=True, rewrite=rw, stream=stream)["ret"]
+            fam = out["family"]
+            with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+                out["rn_ret"] = torch.where(fam == 4, r4, torch.where(fam == 6, r6, torch.zeros_like(r4)))
         return out
 
     _FWDF_KEYS = _FWD_KEYS + ("host_mac", "rewrite")

@@ -985,6 +985,54 @@ def make_ct_stream(rng, n_conn: int, locals_be: np.ndarray, remotes_be: np.ndarr
     return {key: np.ascontiguousarray(v[order]) for key, v in out.items()}
 
 
+def frames_from_ct(t: dict, stride: int = 64, v6: bool = False):
+    """A make_ct_stream dict as Ethernet frames, the counterpart of
+    frames_from_tuples for the stateful path (vectorised): IPv4 without
+    options / IPv6 without extension headers, the stream's ports at l4 + 0 /
+    + 2 of TCP and UDP, l4b in TCP bytes 12-13 or as the ICMP / ICMPv6 type
+    byte, MF set on fragments.  Checksums stay zero: the frames are for the
+    parse and for timing, not for a rewrite.  Returns (frames dict, the stream
+    with len raised to at least the frame's own headers): an IPv6 TCP frame
+    needs 74 bytes, and the stream's 64-67-byte lengths would otherwise end
+    it in DROP_CT_INVALID_HDR.  Bytes that do not fit the slot are dropped
+    (an IPv6 TCP frame in a 64-byte slot: the parse answers DROP_SNAPLEN)."""
+    n = len(t["proto"])
+    proto = np.asarray(t["proto"], np.uint8)
+    l4 = 54 if v6 else 34
+    D = np.zeros((n, max(stride, l4 + 14)), np.uint8)
+    D[:, 0:6] = np.frombuffer(L.NODE_MAC, np.uint8)
+    D[:, 6:12] = np.frombuffer(LXC_MAC, np.uint8)
+    if v6:
+        D[:, 12], D[:, 13] = 0x86, 0xDD
+        D[:, 14] = 0x60
+        D[:, 20] = proto
+        D[:, 21] = 64
+        D[:, 22:38] = np.asarray(t["saddr"], np.uint8).reshape(n, 16)
+        D[:, 38:54] = np.asarray(t["daddr"], np.uint8).reshape(n, 16)
+    else:
+        D[:, 12] = 0x08
+        D[:, 14] = 0x45
+        D[:, 20] = np.where((np.asarray(t["flags"]) >> 1) & 1, 0x20, 0x00)
+        D[:, 22] = 64
+        D[:, 23] = proto
+        D[:, 26:30] = np.ascontiguousarray(t["saddr"], np.uint32).view(np.uint8).reshape(n, 4)
+        D[:, 30:34] = np.ascontiguousarray(t["daddr"], np.uint32).view(np.uint8).reshape(n, 4)
+    tcp, udp = proto == 6, proto == 17
+    icmp = proto == (58 if v6 else 1)
+    tu = tcp | udp
+    D[tu, l4:l4 + 2] = np.ascontiguousarray(t["sport"], np.uint16).view(np.uint8).reshape(n, 2)[tu]
+    D[tu, l4 + 2:l4 + 4] = np.ascontiguousarray(t["dport"], np.uint16).view(np.uint8).reshape(n, 2)[tu]
+    l4b = np.ascontiguousarray(t["l4b"], np.uint16).view(np.uint8).reshape(n, 2)
+    D[tcp, l4 + 12:l4 + 14] = l4b[tcp]
+    D[icmp, l4] = l4b[icmp, 0]
+    hdr = l4 + np.select([tcp, udp, icmp], [20, 8, 8], 0)
+    s = dict(t)
+    s["len"] = np.maximum(np.asarray(t["len"], np.uint32), hdr.astype(np.uint32))
+    f = {"data": np.ascontiguousarray(D[:, :stride]), "len": s["len"].copy(),
+         "flags": (np.asarray(t["flags"]) & 1).astype(np.uint8), "ep": np.asarray(t["ep"], np.uint16).copy()}
+    return f, s
+
+
 def ct_endpoints(n_endpoints: int):
     """Local endpoint addresses (network order, inside the cluster /8) and
     their SECLABELs (lxc_config.h) for the stateful workloads."""

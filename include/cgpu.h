@@ -868,6 +868,42 @@ int cgpu_frames_parse(cgpu_ctx *ctx, const cgpu_frames *f, size_t n,
 		      const cgpu_frame_tuples *out, void *stream);
 
 /*
+ * Frames to the columns of the STATEFUL path: cgpu_frames_parse's steps and
+ * statuses, and for a frame with status 0 the fields ct_lookup4 / ct_lookup6
+ * load from the packet (bpf/lib/conntrack.h:471-530, :317-378) as the columns
+ * cgpu_classify_v4_ct / _v6_ct take (declared further down; len and ep are the
+ * frame's own).  Such a frame has passed every one of those loads: the parse
+ * bounds the TCP 14-byte and UDP 4-byte loads and the ICMP type byte (-135)
+ * and the protocol gate (-137).  A frame with status != 0 gets family, saddr,
+ * daddr, proto and flags as cgpu_frames_parse writes them, and sport, dport
+ * and l4 of 0.  It reads the published snapshot as cgpu_frames_parse does (the
+ * lxc rows, node_mac, router_ip, lb_flags).  IPv4 options and IPv6 extension
+ * headers are followed; every byte read lies within min(len, stride).
+ *
+ * -EINVAL, judged before the context: a null struct, with n > 0 a null status,
+ * data, len, flags or ep, a stride that is not a multiple of 16 or is
+ * below 64, data not 16-byte aligned, a nonzero reserved, a misaligned 2-, 4-
+ * or 16-byte column.  Then -ENODEV on a host-only context, then -EINVAL on a
+ * context with ct_proto_gate == 0 (the stateful path is the CONNTRACK build;
+ * without the gate the parse bounds no L4 load); n == 0 then returns 0.
+ */
+typedef struct cgpu_frame_ct_cols { /* device pointers, n elements each, frame order */
+	int32_t *status;  /* required: exactly cgpu_frames_parse's status */
+	uint8_t *family;  /* 4, 6, 0: as cgpu_frames_parse */
+	uint8_t *saddr;   /* 16 B per frame, 16-byte aligned (IPv4: first 4, rest zero) */
+	uint8_t *daddr;
+	uint16_t *sport;  /* the u16 at l4 + 0 as loaded (network order), TCP / UDP; else 0 */
+	uint16_t *dport;  /* the u16 at l4 + 2, TCP / UDP; else 0 (the WIRE port, not the
+			     policy tuple's dport that cgpu_frames_parse reports) */
+	uint8_t *proto;
+	uint16_t *l4;     /* cgpu_tuples_v4_ct.l4: TCP the u16 loaded at l4 + 12 (byte 12 in
+			     the low half); ICMP / ICMPv6 the type byte at l4; UDP 0 */
+	uint8_t *flags;   /* CGPU_F_EGRESS | CGPU_F_FRAGMENT as cgpu_frames_parse */
+} cgpu_frame_ct_cols;
+int cgpu_frames_parse_ct(cgpu_ctx *ctx, const cgpu_frames *f, size_t n,
+			 const cgpu_frame_ct_cols *out, void *stream);
+
+/*
  * Raw frames to verdicts in one pass: cgpu_frames_parse, then for frames
  * that reach policy the decision of cgpu_classify_v4 / cgpu_classify_v6 on
  * that tuple (mixed IPv4 / IPv6 batches).  Frames that end before policy get
@@ -1402,6 +1438,65 @@ int cgpu_rnat_frames_v4(cgpu_ctx *ctx, const cgpu_rnf4_in *in, uint32_t flags, s
 			int32_t *ret /* may be NULL */, void *stream);
 int cgpu_rnat_frames_v6(cgpu_ctx *ctx, const cgpu_rnf6_in *in, uint32_t flags, size_t n,
 			int32_t *ret /* may be NULL */, void *stream);
+
+/*
+ * The stateful decision on a mixed batch of raw frames: cgpu_frames_parse_ct,
+ * then the conntrack calls on the frames that reach conntrack, their results
+ * back at the frames' indices.  The call pins ONE snapshot for all it does.
+ *
+ * A frame with status 0 and family 4 is a packet of cgpu_classify_v4_ct (with
+ * the rn group given: of cgpu_classify_v4_ct_rnat), one with family 6 a packet
+ * of cgpu_classify_v6_ct (_rnat), on the columns of cgpu_frames_parse_ct and
+ * the frame's len and ep.  The packets of each family run in frame order; the
+ * two families use different maps (cilium_ct4_global, cilium_ct6_global), so
+ * the result is that of processing the whole batch in order.  Each such
+ * frame's verdict, ct_ret, identity, stage and rn elements are that call's
+ * outputs for that packet (rn_saddr4 / rn_daddr4 of an IPv6 frame and
+ * rn_saddr6 of an IPv4 frame are 0).  Policy counters, metrics, the conntrack
+ * maps and LRU mode (ct_lru) are those calls', because those calls run.
+ *
+ * A frame that ends before conntrack (status != 0) gets cgpu_classify_frames'
+ * result: verdict = status (0 for CGPU_FRAME_NOT_CLASSIFIED), identity 0,
+ * stage 5 (4 for DROP_CT_UNKNOWN_PROTO, 7 for not classified), ct_ret
+ * CGPU_CT_NONE, every rn element 0; it is counted in the metrics once at
+ * {reason = (-status) & 0xff, dir} with its len, not-classified and
+ * CGPU_DROP_SNAPLEN frames not at all.  For a -137 frame that is what
+ * cgpu_classify_v4_ct reports for a packet of that protocol.
+ *
+ * The plain conntrack form: no service step runs in front (a _ctlb form on
+ * frames does not exist).  cgpu_rnat_frames_v4 / _v6 take the rn columns as
+ * they are, one call per family on the same frames: each leaves the other
+ * family's frames alone.
+ *
+ * Scratch: per context, grow-only, freed by cgpu_ctx_destroy; 125 bytes per
+ * frame of the largest batch seen (the parsed columns 42, two index lists 8,
+ * the compacted packets and their results at most 75) besides the conntrack
+ * calls' own.  Calls on one context serialise on it.  Like the conntrack
+ * calls, the call waits on the host (once on `stream` for the two packet
+ * counts, beside those calls' own wait) and may allocate: it cannot be
+ * captured into a graph.
+ *
+ * -EINVAL, judged before the context: cgpu_frames_parse_ct's argument rules
+ * (status and family are optional here; verdict, ct_ret and identity
+ * required), an rn group given in part, a misaligned column, n > INT32_MAX.
+ * Then -ENODEV on a host-only context, then -EINVAL with ct_proto_gate == 0;
+ * n == 0 then returns 0.
+ */
+typedef struct cgpu_fct_out { /* device pointers, n elements each, frame order */
+	int32_t *status;   /* optional: the parse's status */
+	uint8_t *family;   /* optional */
+	int32_t *verdict;  /* required */
+	uint8_t *ct_ret;   /* required */
+	uint32_t *identity; /* required */
+	uint8_t *stage;    /* optional */
+	/* reverse NAT: all five NULL (the plain calls run) or all five given (the _rnat calls run) */
+	uint8_t *rn_applied;
+	uint16_t *rn_sport;
+	uint32_t *rn_saddr4, *rn_daddr4; /* cgpu_rnat4_out.saddr / .daddr of the IPv4 frames */
+	uint8_t *rn_saddr6;              /* [n][16], 16-byte aligned: cgpu_rnat6_out.saddr */
+} cgpu_fct_out;
+int cgpu_classify_frames_ct(cgpu_ctx *ctx, const cgpu_frames *f, size_t n, uint32_t now,
+			    const cgpu_fct_out *out, void *stream);
 
 /* ------------------------------------------------------------------ */
 /* checkpoint / resume                                      */
