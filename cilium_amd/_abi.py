@@ -231,8 +231,7 @@ PROTOS = {
     "cgpu_table_verify": (i32, [vp]),
     "cgpu_mirror_save": (i32, [vp, C.c_char_p]),
     "cgpu_mirror_restore": (i32, [vp, C.c_char_p]),
-    "cgpu__test_corrupt": (i32, [vp, i32, sz, C.c_uint8]),
-    "cgpu_counter_layout_checksum": (i32, [vp, C.POINTER(u64)]),
+    "cgpu__test_corrupt": (i32, [vp, i32, sz, C.c_uint8]),    "cgpu_counter_layout_checksum": (i32, [vp, C.POINTER(u64)]),
     "cgpu_classify_v4": (i32, [vp, C.POINTER(TuplesV4), sz, vp, vp, vp, vp]),
     "cgpu_classify_v4_host": (i32, [vp, C.POINTER(TuplesV4), sz, vp, vp, vp, vp]),
     "cgpu_classify_v6": (i32, [vp, C.POINTER(TuplesV6), sz, vp, vp, vp, vp]),
@@ -308,6 +307,14 @@ PROTOS = {
     "cgpu_counters_allreduce": (i32, [vp, vp]),
 }
 
+# test hooks that no header declares and PROTOS (the header's table) leaves
+# out; typed here when the loaded library has them
+TEST_HOOKS = {
+    # the split x16 slots of the IPv4 ipcache tables (tables.h LPMC_SPLIT):
+    # keys, vals, del, n, n_first, out[16], commits[2]
+    "cgpu_diag_ipc4_split": (i32, [vp, vp, vp, sz, sz, vp, vp]),
+}
+
 _lib = None
 
 
@@ -328,6 +335,10 @@ def lib():
             f = getattr(L, name)
             f.restype = res
             f.argtypes = args
+        for name, (res, args) in TEST_HOOKS.items():
+            f = getattr(L, name, None)
+            if f is not None:
+                f.restype, f.argtypes = res, args
         _lib = L
     return _lib
 

@@ -192,7 +192,7 @@ struct Dir248 {
 struct Lpm16cBuild {
 	std::vector<uint32_t> d16, nodes, x16, dict;
 	std::unordered_map<uint32_t, uint32_t> code; /* leaf -> dict index */
-	size_t nodes_at_build = 0;
+	size_t nodes_at_build = 0, kids_at_build = 0;
 	/* run list over one block: (start, leaf) with distinct neighbours */
 	typedef std::vector<std::pair<uint32_t, uint32_t>> Runs;
 	static void push(Runs &r, uint32_t start, uint32_t v)
@@ -236,12 +236,12 @@ struct Lpm16cBuild {
 			return emit_node(r);
 		return emit_array(leaf);
 	}
-	/* the runs of /16 p (stops collecting past LPMC_MAX_RUN_BOUNDS + 1) */
+	/* the runs of /16 p (stops collecting past LPMC_SPLIT_MAX_RUNS) */
 	static Runs runs16(uint32_t p, const std::vector<uint32_t> &tbl24, const std::vector<uint32_t> &tbl8)
 	{
 		Runs r;
 		const uint32_t *t = &tbl24[(size_t)p * 256];
-		for (uint32_t j = 0; j < 256 && r.size() <= LPMC_MAX_RUN_BOUNDS + 1; j++) {
+		for (uint32_t j = 0; j < 256 && r.size() <= LPMC_SPLIT_MAX_RUNS; j++) {
 			if ((t[j] & DIR_TAG_MASK) != DIR_TAG_GROUP) {
 				push(r, j << 8, t[j]);
 				continue;
@@ -268,6 +268,48 @@ struct Lpm16cBuild {
 					 : byte_level(&tbl8[(size_t)(t[j] & DIR_PAYLOAD_MASK) * 256]);
 		return emit_array(ent);
 	}
+	/* words of x16 behind the 65,536 slots: the split slots' children */
+	size_t kid_words() const { return x16.size() > (size_t)65536 * 4 ? x16.size() - (size_t)65536 * 4 : 0; }
+	/* an inline-format node of runs r[at .. at + n), n <= 5 */
+	void inline_node(uint32_t *w, const Runs &r, size_t at, uint32_t n)
+	{
+		const uint32_t k = n - 1;
+		uint64_t v = 0;
+		w[0] = w[1] = 0;
+		for (uint32_t i = 0; i < 4; i++) {
+			uint32_t b = i < k ? r[at + i + 1].first : 0xFFFFu;
+			w[i / 2] |= (i & 1) ? (b << 16) : b;
+		}
+		for (uint32_t i = 0; i < 5; i++)
+			v |= (uint64_t)code.at(r[at + std::min(i, k)].second) << (12 * i);
+		w[2] = (uint32_t)v;
+		w[3] = (uint32_t)(v >> 32);
+	}
+	/* the overflow slot of /16 p as a split slot (tables.h LPMC_SPLIT): 5..24
+	 * run starts, every leaf with a code; appends the children to x16 */
+	void split16(uint32_t p, const Runs &r)
+	{
+		const size_t n = r.size();
+		if (n < 6 || n > LPMC_SPLIT_MAX_RUNS)
+			return;
+		for (auto &x : r)
+			if (!code.count(x.second))
+				return;
+		const uint32_t nch = (uint32_t)(n + 4) / 5;
+		const size_t base = x16.size() / 4;
+		if (base + nch - 1 > LPMC_SPLIT_BASE_MASK)
+			return;
+		x16.resize(x16.size() + (size_t)nch * 4, 0u);
+		uint32_t *w = &x16[(size_t)p * 4];
+		w[1] = w[2] = 0xFFFFFFFFu;
+		for (uint32_t j = 1; j < nch; j++) {
+			const uint32_t c = r[(size_t)5 * j].first, sh = (j - 1) & 1 ? 16u : 0u;
+			w[1 + (j - 1) / 2] = (w[1 + (j - 1) / 2] & ~(0xFFFFu << sh)) | (c << sh);
+		}
+		for (uint32_t j = 0; j < nch; j++)
+			inline_node(&x16[(base + j) * 4], r, (size_t)5 * j, (uint32_t)std::min<size_t>(5, n - (size_t)5 * j));
+		w[3] = LPMC_OVERFLOW | LPMC_SPLIT | ((nch - 1) << LPMC_SPLIT_LAST_SHIFT) | (uint32_t)base;
+	}
 	/* x16[p]: inline when <= 4 run starts and every leaf has a dict code */
 	void inline16(uint32_t p, const Runs &r)
 	{
@@ -279,18 +321,10 @@ struct Lpm16cBuild {
 		if (!inl) {
 			w[0] = d16[p];
 			w[3] = LPMC_OVERFLOW;
+			split16(p, r); /* (may move x16: w is dead) */
 			return;
 		}
-		const uint32_t k = (uint32_t)r.size() - 1;
-		uint64_t v = 0;
-		for (uint32_t i = 0; i < 4; i++) {
-			uint32_t b = i < k ? r[i + 1].first : 0xFFFFu;
-			w[i / 2] |= (i & 1) ? (b << 16) : b;
-		}
-		for (uint32_t i = 0; i < 5; i++)
-			v |= (uint64_t)code.at(r[std::min(i, k)].second) << (12 * i);
-		w[2] = (uint32_t)v;
-		w[3] = (uint32_t)(v >> 32);
+		inline_node(w, r, 0, (uint32_t)r.size());
 	}
 	/* full build: dictionary = the LPMC_DICT most frequent leaves of
 	 * inline-able /16s */
@@ -327,6 +361,7 @@ struct Lpm16cBuild {
 		for (uint32_t p = 0; p < 65536; p++)
 			inline16(p, all[p]);
 		nodes_at_build = nodes.size();
+		kids_at_build = kid_words();
 	}
 	/* recompile /16s [lo, hi] after their DIR-24-8 entries changed; new
 	 * leaves join the dictionary while it has room */
@@ -344,8 +379,11 @@ struct Lpm16cBuild {
 			inline16(p, r);
 		}
 	}
-	/* replaced nodes outweigh live ones: time for a full build */
-	bool bloated() const { return nodes.size() > 2 * nodes_at_build + (1u << 16); }
+	/* replaced nodes (and split children) outweigh live ones: time for a full build */
+	bool bloated() const
+	{
+		return nodes.size() + kid_words() > 2 * (nodes_at_build + kids_at_build) + (1u << 16);
+	}
 };
 
 struct Rank4 {
@@ -4745,6 +4783,14 @@ CGPU_EXPORT int cgpu__test_corrupt(cgpu_ctx *c, int group, size_t off, uint8_t m
 static uint32_t lpmc_host_lookup(const Lpm16cBuild &t, uint32_t h)
 {
 	const uint32_t *q = &t.x16[(size_t)(h >> 16) * 4];
+	if ((q[3] & (LPMC_OVERFLOW | LPMC_SPLIT)) == (LPMC_OVERFLOW | LPMC_SPLIT)) {
+		/* a split slot: the child that covers x, an inline-format node */
+		const uint32_t x = h & 0xFFFFu;
+		const uint32_t k = (x >= (q[1] & 0xFFFFu)) + (x >= (q[1] >> 16)) + (x >= (q[2] & 0xFFFFu)) +
+				   (x >= (q[2] >> 16));
+		q = &t.x16[((size_t)(q[3] & LPMC_SPLIT_BASE_MASK) +
+			    std::min(k, (q[3] >> LPMC_SPLIT_LAST_SHIFT) & 7u)) * 4];
+	}
 	if (!(q[3] & LPMC_OVERFLOW)) {
 		const uint32_t x = h & 0xFFFFu;
 		const uint32_t cnt = (x >= (q[0] & 0xFFFFu)) + (x >= (q[0] >> 16)) + (x >= (q[1] & 0xFFFFu)) +
@@ -4934,6 +4980,61 @@ CGPU_EXPORT int cgpu_diag_ipc4_shapes(const cgpu_ipcache_key *keys, const cgpu_r
 	if (!rc) {
 		lpmc_shapes(c->b.lc, out);
 		lpmc_shapes(c->b.lcT, out + 16);
+	}
+	if (commits) {
+		commits[0] = c->b.ipc_builds;
+		commits[1] = c->b.ipc_patched;
+	}
+	cgpu_ctx_destroy(c);
+	return rc;
+}
+
+/* the split slots of one compiled lpm16c table: cgpu_diag_ipc4_split */
+static void lpmc_split_counts(const Lpm16cBuild &t, const Dir248 &d, uint32_t *o)
+{
+	if (t.x16.empty())
+		return;
+	o[6] = (uint32_t)t.kid_words();
+	for (uint32_t p = 0; p < 65536; p++) {
+		const uint32_t *q = &t.x16[(size_t)p * 4];
+		if (!(q[3] & LPMC_OVERFLOW))
+			continue;
+		if (q[3] & LPMC_SPLIT) {
+			const uint32_t last = (q[3] >> LPMC_SPLIT_LAST_SHIFT) & 7u;
+			o[last - 1]++;
+			o[7] += (last + 1) * 4;
+			continue;
+		}
+		const size_t starts = Lpm16cBuild::runs16(p, d.tbl24, d.tbl8).size() - 1;
+		if (starts >= LPMC_SPLIT_MAX_RUNS)
+			o[5]++;
+		else if (starts >= 5)
+			o[4]++;
+	}
+}
+
+/* Test hook (no header): the split slots (tables.h LPMC_SPLIT) of the IPv4
+ * ipcache tables compiled as cgpu_diag_ipc_tunnel compiles them (same
+ * arguments up to n_first).  out[0..7]: the identity table, out[8..15]: the
+ * tunnel table:
+ *   [0..3] the number of /16s split into 2..5 children; [4] /16s of 5..24 run
+ *   starts left unsplit for want of a dictionary code; [5] /16s past 24 run
+ *   starts; [6] words of x16 behind the 65,536 slots (children, replaced ones
+ *   included); [7] the words of them that a split slot refers to.
+ * commits (may be NULL): {IPv4 full builds, commits that patched}. */
+CGPU_EXPORT int cgpu_diag_ipc4_split(const cgpu_ipcache_key *keys, const cgpu_remote_endpoint_info *vals,
+				     const uint8_t *del, size_t n, size_t n_first, uint32_t *out, uint64_t *commits)
+{
+	if ((n && (!keys || !vals)) || !out || n_first > n)
+		return fail(-EINVAL, "null argument");
+	cgpu_ctx *c = nullptr;
+	const int rc = diag_ipc_compile(keys, vals, del, n, n_first, &c);
+	if (!c)
+		return rc;
+	memset(out, 0, 16 * sizeof(uint32_t));
+	if (!rc) {
+		lpmc_split_counts(c->b.lc, c->b.dir, out);
+		lpmc_split_counts(c->b.lcT, c->b.dirT, out + 8);
 	}
 	if (commits) {
 		commits[0] = c->b.ipc_builds;

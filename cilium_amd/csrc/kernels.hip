@@ -2517,15 +2517,40 @@ __global__ __launch_bounds__(NT, MINW) void k_classify_x4(cgpu_snapshot s, cls_a
 						s.ipc4c.x16)[act[u] ? DIAG_LPM(bswap32(ad[u]) >> 16) : 0u];
 				}
 				whole_q<Q>(q);
+				/* a split slot (tables.h LPMC_SPLIT): the child that covers
+				 * x, one more 16-byte gather for the Q tuples together (a
+				 * tuple without one reads slot 0), decoded as an inline
+				 * node is.  The x16 slot leaves only its code or word 0. */
+				uint4 c[Q];
+				bool spl[Q], inl[Q];
+				uint32_t w0[Q], ci[Q];
 #pragma unroll
 				for (int u = 0; u < Q; u++) {
-					const bool inl = act[u] && !(q[u].w & LPMC_OVERFLOW);
+					inl[u] = act[u] && !(q[u].w & LPMC_OVERFLOW);
+					spl[u] = act[u] && (q[u].w & (LPMC_OVERFLOW | LPMC_SPLIT)) == (LPMC_OVERFLOW | LPMC_SPLIT);
 					const uint32_t x = bswap32(ad[u]) & 0xFFFFu;
 					const uint32_t cnt = (x >= (q[u].x & 0xFFFFu) ? 1u : 0u) + (x >= (q[u].x >> 16) ? 1u : 0u) +
 							     (x >= (q[u].y & 0xFFFFu) ? 1u : 0u) + (x >= (q[u].y >> 16) ? 1u : 0u);
+					const uint32_t k = (x >= (q[u].y & 0xFFFFu) ? 1u : 0u) + (x >= (q[u].y >> 16) ? 1u : 0u) +
+							   (x >= (q[u].z & 0xFFFFu) ? 1u : 0u) + (x >= (q[u].z >> 16) ? 1u : 0u);
+					const uint32_t last = (q[u].w >> LPMC_SPLIT_LAST_SHIFT) & 7u;
 					const uint64_t v = ((uint64_t)q[u].w << 32) | q[u].z;
-					const uint32_t leaf = ldict[inl ? (uint32_t)(v >> (12u * cnt)) & 0xFFFu : 0u];
-					e[u] = !act[u] ? 0u : (inl ? leaf : q[u].x);
+					ci[u] = spl[u] ? (q[u].w & LPMC_SPLIT_BASE_MASK) + (k < last ? k : last) : 0u;
+					w0[u] = inl[u] ? (uint32_t)(v >> (12u * cnt)) & 0xFFFu : q[u].x;
+				}
+#pragma unroll
+				for (int u = 0; u < Q; u++)
+					c[u] = reinterpret_cast<const uint4 *>(s.ipc4c.x16)[ci[u]];
+				whole_q<Q>(c);
+#pragma unroll
+				for (int u = 0; u < Q; u++) {
+					const uint32_t x = bswap32(ad[u]) & 0xFFFFu;
+					const uint32_t cnt = (x >= (c[u].x & 0xFFFFu) ? 1u : 0u) + (x >= (c[u].x >> 16) ? 1u : 0u) +
+							     (x >= (c[u].y & 0xFFFFu) ? 1u : 0u) + (x >= (c[u].y >> 16) ? 1u : 0u);
+					const uint64_t v = ((uint64_t)c[u].w << 32) | c[u].z;
+					const uint32_t code = spl[u] ? (uint32_t)(v >> (12u * cnt)) & 0xFFFu : w0[u];
+					const uint32_t leaf = ldict[inl[u] || spl[u] ? code : 0u];
+					e[u] = !act[u] ? 0u : (inl[u] || spl[u] ? leaf : w0[u]);
 				}
 			} else {
 				/* one 16-byte gather: the /16's inline run node (tables.h) */
@@ -2574,9 +2599,52 @@ __global__ __launch_bounds__(NT, MINW) void k_classify_x4(cgpu_snapshot s, cls_a
 					e[u] = (fw[u] & (F_OK | F_GATED | F_LBDROP)) == F_OK ? ldict[(uint32_t)(v >> (12u * cnt)) & 0xFFFu] : 0u;
 				}
 			}
+#ifdef CGPU_DIAG_LPM_ONE_GATHER /* timing-only tool build (tools/diag_ab.py): wrong identities */
+			if constexpr (QX) {
+				/* what an overflowing /16 would cost as ONE 16-byte gather:
+				 * a node's 16 bytes that hold a leaf in word 1 (an array's
+				 * first four entries), no array level, no search, no far leaf */
+				bool grpn[Q], anyn = false;
+#pragma unroll
+				for (int u = 0; u < Q; u++) {
+					grpn[u] = (e[u] & DIR_TAG_MASK) == DIR_TAG_GROUP;
+					anyn |= grpn[u];
+				}
+				if (__ballot(anyn)) {
+					uint4 q[Q];
+#pragma unroll
+					for (int u = 0; u < Q; u++) {
+						const uint32_t kind = (e[u] >> LPMC_KIND_SHIFT) & 3u;
+						q[u] = *(grpn[u] ? reinterpret_cast<const uint4 *>(s.ipc4c.nodes) +
+									   (e[u] & LPMC_OFF_MASK) + (kind == 1u || kind == 2u ? 1 : 0)
+								 : reinterpret_cast<const uint4 *>(s.ipc4c.x16));
+					}
+					whole_q<Q>(q);
+#pragma unroll
+					for (int u = 0; u < Q; u++) {
+						/* (an array's entry may be a reference: keep a leaf's tag) */
+						const uint32_t r = (q[u].y & DIR_TAG_MASK) == DIR_TAG_GROUP
+									   ? DIR_TAG_DIRECT | (q[u].y & 0xFFFFu)
+									   : q[u].y;
+						e[u] = grpn[u] ? r : e[u];
+					}
+				}
+			} else
+#endif
 			{
 				/* compressed LPM (tables.h lpm16c): arrays (rare), then one run node */
 				constexpr uint32_t ARR = (DIR_TAG_GROUP >> LPMC_KIND_SHIFT) | 3u;
+				/* (QX: both array levels behind one wave-uniform branch; a
+				 * table whose overflowing /16s are all split has no wave
+				 * that enters) */
+				bool anya = !QX;
+				if constexpr (QX) {
+#pragma unroll
+					for (int u = 0; u < Q; u++)
+						anya |= (e[u] >> LPMC_KIND_SHIFT) == ARR;
+					anya = __ballot(anya) != 0;
+				}
+				if (anya) {
 #pragma unroll
 				for (int u = 0; u < Q; u++)
 					if ((e[u] >> LPMC_KIND_SHIFT) == ARR) {
@@ -2588,6 +2656,7 @@ __global__ __launch_bounds__(NT, MINW) void k_classify_x4(cgpu_snapshot s, cls_a
 				for (int u = 0; u < Q; u++)
 					if ((e[u] >> LPMC_KIND_SHIFT) == ARR)
 						e[u] = s.ipc4c.nodes[(size_t)(e[u] & LPMC_OFF_MASK) * 4u + (bswap32(ad[u]) & 255u)];
+				}
 				if constexpr (QX) {
 					/* the first 32 bytes of every tuple's node in flight
 					 * together: all the run starts of a node (lpmc_search:
@@ -2596,9 +2665,9 @@ __global__ __launch_bounds__(NT, MINW) void k_classify_x4(cgpu_snapshot s, cls_a
 					 * word, gathered for the Q tuples together behind a
 					 * wave-uniform branch (most quads have none); its whole
 					 * second half for four tuples does not fit the register
-					 * file.  A tuple without a node reads x16's slot 0, a
-					 * 16-byte node its only 16 bytes again (`nodes` may be
-					 * empty) */
+					 * file.  A tuple without a node reads x16's slot 0, and
+					 * so does the second load of a 16-byte node (`nodes` may
+					 * be empty; words 4..7 of such a node are never its leaf) */
 					bool grpn[Q], far[Q], anyn = false, anyf = false;
 					uint32_t kind[Q], idx[Q];
 #pragma unroll
@@ -2615,7 +2684,7 @@ __global__ __launch_bounds__(NT, MINW) void k_classify_x4(cgpu_snapshot s, cls_a
 											    (e[u] & LPMC_OFF_MASK)
 										  : reinterpret_cast<const uint4 *>(s.ipc4c.x16);
 							q[u][0] = nd[0];
-							q[u][1] = nd[kind[u] ? 1 : 0];
+							q[u][1] = *(kind[u] ? nd + 1 : reinterpret_cast<const uint4 *>(s.ipc4c.x16));
 						}
 #pragma unroll
 						for (int u = 0; u < Q; u++) {

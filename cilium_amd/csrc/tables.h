@@ -61,12 +61,28 @@
  * (the LPMC_DICT most frequent leaves get one). */
 #define LPMC_DICT 4095u
 #define LPMC_OVERFLOW (1u << 31)
+/* A SPLIT overflow slot: a /16 of 5..24 run starts whose leaves all have
+ * codes, answered by ONE further 16-byte gather.  Word 0 and bit 63 are an
+ * overflow slot's (a reader that knows nothing of the split walks `nodes` as
+ * before), and
+ *   words 1..2: u16 coarse run starts c_1..c_4 (unused 0xFFFF)
+ *   word 3:     bit 30 set; bits 27..29 the last child's index L (1..4);
+ *               bits 0..26 B, the first child's slot in x16 (the children
+ *               live behind the 65,536 /16 slots)
+ * child min(#{i : c_i <= x}, L) is x16[B + ..], a node in exactly the inline
+ * format over the same x (bit 63 clear): five runs each, the last one fewer
+ * maybe.  The plain x4 classify kernel takes this form; patched-away children
+ * are garbage until the next full build. */
+#define LPMC_SPLIT (1u << 30)
+#define LPMC_SPLIT_LAST_SHIFT 27u
+#define LPMC_SPLIT_BASE_MASK ((1u << LPMC_SPLIT_LAST_SHIFT) - 1u)
+#define LPMC_SPLIT_MAX_RUNS 25u
 
 typedef struct lpm16c {
 	const uint32_t *d16;   /* 65536 entries; NULL = not compiled */
 	const uint32_t *nodes; /* 16-byte aligned */
 	const uint32_t *vals;
-	const uint32_t *x16;   /* 65536 x 4 words (inline run nodes) */
+	const uint32_t *x16;   /* 65536 x 4 words (inline run nodes), then the split slots' children */
 	const uint32_t *dict;  /* leaf per code */
 	uint32_t n_node_words;
 	uint32_t n_dict;

@@ -26,7 +26,11 @@ VARIANTS = {"product": (), "no_cold_atomics": ("CGPU_DIAG_NO_COLD",),
             "nc_lpm_l2": ("CGPU_DIAG_NO_COLD", "CGPU_DIAG_LPM_SMALL"),
             "nc_all_l2": ("CGPU_DIAG_NO_COLD", "CGPU_DIAG_P1_SMALL", "CGPU_DIAG_P2_SMALL",
                           "CGPU_DIAG_LPM_SMALL"),
-            "one_wg_per_cu": ("CGPU_DIAG_LDS_PAD=65536",),
+            # the plain x4 kernel with every overflowing /16 answered by x16 plus ONE
+            # 16-byte gather (no array level, no run search, no far leaf): the
+            # ceiling of a split x16 slot, profiles/lpm_split/
+            "lpm_one_gather": ("CGPU_DIAG_LPM_ONE_GATHER",),
+            "one_wg_per_cu":("CGPU_DIAG_LDS_PAD=65536",),
             "store_sc1": ("CGPU_DIAG_STORE_SC1",),
             "pf6_no_node": ("CGPU_DIAG_PF6_NO_NODE",), "pf6_no_ep": ("CGPU_DIAG_PF6_NO_EP",),
             "pf6_no_cover": ("CGPU_DIAG_PF6_NO_COVER",),
